@@ -13,9 +13,13 @@ FIFO iteration (weak scaling, windows are independent) and the window outputs ar
 all_gather per step — the same message tokensgen_amd/fifo.py sends (2 x 13 frames per window + the rank's
 failure flag).
 
-Prints ONE JSON line (rank 0).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times `--steps` steps and prints the headline (`value`, `ms_per_step`, ...);
+`--full` adds everything else on the record (per-kernel and roofline times, the other attention path, power and clock, the zero-operand
+control, the VAE and training sub-records, the CPU baseline) and writes the full record to the detail file.  `--dump-outputs DIR` saves what
+the last timed step returned, as float32 .npy; the inputs are seeded, so equal arguments give equal inputs.
 """
 import argparse
+import contextlib
 import json
 import os
 import re
@@ -746,6 +750,13 @@ def emit(out):
     sys.stdout.flush()
 
 
+def dump_outputs(d, arrays):
+    """`arrays` (name -> device tensor, what a caller of the timed path receives) as float32 `d/<name>.npy`: the files two builds are compared on."""
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), t.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -757,11 +768,21 @@ def main():
                          "gen: e2e preceded by the T2To token stage (gen.yaml, BASELINE config 3); train: To2V training micro-steps (BASELINE config 5)")
     ap.add_argument("--accum", type=int, default=9, help="--mode train: gradient_accumulation_steps (yaml: 9)")
     ap.add_argument("--chunks", type=int, default=12, help="--mode e2e: number of 49-frame clips (edit.yaml: 12)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-vae", action="store_true", help="skip the VAE (BASELINE config 4) sub-record")
-    ap.add_argument("--no-train", action="store_true", help="skip the training (BASELINE config 5) sub-record")
-    ap.add_argument("--no-zero-control", action="store_true", help="skip the zero-operand control (3 untimed steps on zeroed weights and inputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="window mode: besides the headline, the full record — attention launches timed with HIP events, the other attention path, power and clock, "
+                         "zero-operand control, VAE and training sub-records, CPU baseline — written to the detail file; without it only setup, warm-up, the timed steps "
+                         "and the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="window mode: write what the last timed step returned (window latents and x0) to DIR/<name>.npy as float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-vae", action="store_true", help="--full: skip the VAE (BASELINE config 4) sub-record")
+    ap.add_argument("--no-train", action="store_true", help="--full: skip the training (BASELINE config 5) sub-record")
+    ap.add_argument("--no-zero-control", action="store_true", help="--full: skip the zero-operand control (3 untimed steps on zeroed weights and inputs)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and a.mode != "window":
+        ap.error("--dump-outputs applies to --mode window")
 
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU: the hot path has no CPU fallback")
@@ -835,7 +856,7 @@ def main():
             buf = xbuf[:n_el].view(2, nf, C, H, W)
             buf[0], buf[1] = x[0], x0
             dist.all_gather_into_tensor(gathered, xbuf)
-        return x
+        return x, x0
 
     def fence():
         torch.cuda.synchronize()
@@ -846,70 +867,75 @@ def main():
     for _ in range(a.warmup):
         step()
     fence()
-    # inside the timed region only the dominant kernel's launches are bracketed by HIP events (on the launch stream); the other
-    # kernels' durations come from one extra, untimed step afterwards, so their ~1800 event markers do not sit in the measurement
     ATTN = "attention_2seg+rider"
-    K.PROFILE.clear(); K.PROFILE_FILTER[0] = {ATTN}; K.PROFILE_ON[0] = True
-    power = PowerSampler(local_rank)                 # a host thread reading sysfs / amdsmi: no GPU work, nothing on the launch stream
+    if a.full:
+        # inside the timed region only the dominant kernel's launches are bracketed by HIP events (on the launch stream); the other
+        # kernels' durations come from one extra, untimed step afterwards, so their ~1800 event markers do not sit in the measurement
+        K.PROFILE.clear(); K.PROFILE_FILTER[0] = {ATTN}; K.PROFILE_ON[0] = True
+    # --full: a host thread reading sysfs / amdsmi: no GPU work, nothing on the launch stream
+    power = PowerSampler(local_rank) if a.full else contextlib.nullcontext()
     with power:
         t0 = time.perf_counter()
         for _ in range(a.steps):
-            x_last = step()
+            x_last, x0_last = step()
         fence()
         dt = time.perf_counter() - t0
-    K.PROFILE_ON[0] = False
-    power = power.summary()
-    attn_prof = K.profile_summary().get(ATTN, {"ms": float("nan"), "n": 0})
     attn_path = model.attn_path                      # what the timed region ran on ("constant_shift" unless the retry counter said otherwise)
-    retry_ws = next(iter(model._ws.values())).retry
-    retried = retry_ws.count()
     finite = bool(torch.isfinite(x_last).all())
-    K.PROFILE.clear(); K.PROFILE_FILTER[0] = None; K.PROFILE_ON[0] = True
-    step()
-    fence()
-    K.PROFILE_ON[0] = False
-    all_prof = K.profile_summary()
-    # the other attention path, one untimed step, so that the headline's dependence on the path is on the record
-    other = "running_max" if attn_path == "constant_shift" else "constant_shift"
-    model.attn_path = other
-    K.PROFILE.clear(); K.PROFILE_FILTER[0] = {ATTN}; K.PROFILE_ON[0] = True
-    t1 = time.perf_counter()
-    step()
-    fence()
-    other_step_ms = 1e3 * (time.perf_counter() - t1)
-    K.PROFILE_ON[0] = False
-    other_prof = K.profile_summary().get(ATTN, {"ms": float("nan"), "n": 0})
-    model.attn_path = attn_path
-    # zero-operand control (untimed, rank-local, AFTER everything that needs the weights): the same launches on all-zero weights and inputs.  With nothing
-    # toggling in the matrix pipe the chip is no longer on its socket power cap; the ratio to `ms_per_step` is how much of the headline is clock, not schedule
-    zero_ctl = None
-    if world == 1 and not a.no_zero_control:
-        keep = {k: t.clone() for k, t in model._fused.items()}
-        for t_ in model._fused.values():
-            t_.zero_()
-        zl, zx0, zp, ze = latents.clone(), old_x0.clone(), prompt.clone(), emb.clone()
-        latents.zero_(); old_x0.zero_(); prompt.zero_(); emb.zero_()
-        znoise = torch.zeros(nf, 2, C, H, W, device=device, dtype=bf)
-
-        def zstep():
-            return worker.window_step(latents, old_x0, has_old, t, prev_t, next_t, znoise, grid_t, cond_t, emb)
-        zstep(); fence()
-        K.PROFILE.clear(); K.PROFILE_FILTER[0] = {ATTN}; K.PROFILE_ON[0] = True
-        zpow = PowerSampler(local_rank)
-        with zpow:
-            t1 = time.perf_counter()
-            for _ in range(3):
-                zx = zstep()
-            fence()
-            zdt = time.perf_counter() - t1
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"latents": x_last, "x0": x0_last})
+    if a.full:
         K.PROFILE_ON[0] = False
-        zattn = K.profile_summary().get(ATTN, {"ms": float("nan"), "n": 0})
-        zero_ctl = {"what": "the same 3 window steps with every weight and every input zeroed (same launches, same schedules; timing only)", "steps": 3,
-                    "ms_per_step": 1e3 * zdt / 3, "attention_launch_ms": zattn["ms"], "finite": bool(torch.isfinite(zx[0]).all()), **zpow.summary()}
-        for k, t_ in model._fused.items():
-            t_.copy_(keep[k])
-        latents.copy_(zl); old_x0.copy_(zx0); prompt.copy_(zp); emb.copy_(ze)
-        del keep, zl, zx0, zp, ze
+        power = power.summary()
+        attn_prof = K.profile_summary().get(ATTN, {"ms": float("nan"), "n": 0})
+        retry_ws = next(iter(model._ws.values())).retry
+        retried = retry_ws.count()
+        K.PROFILE.clear(); K.PROFILE_FILTER[0] = None; K.PROFILE_ON[0] = True
+        step()
+        fence()
+        K.PROFILE_ON[0] = False
+        all_prof = K.profile_summary()
+        # the other attention path, one untimed step, so that the headline's dependence on the path is on the record
+        other = "running_max" if attn_path == "constant_shift" else "constant_shift"
+        model.attn_path = other
+        K.PROFILE.clear(); K.PROFILE_FILTER[0] = {ATTN}; K.PROFILE_ON[0] = True
+        t1 = time.perf_counter()
+        step()
+        fence()
+        other_step_ms = 1e3 * (time.perf_counter() - t1)
+        K.PROFILE_ON[0] = False
+        other_prof = K.profile_summary().get(ATTN, {"ms": float("nan"), "n": 0})
+        model.attn_path = attn_path
+        # zero-operand control (untimed, rank-local, AFTER everything that needs the weights): the same launches on all-zero weights and inputs.  With nothing
+        # toggling in the matrix pipe the chip is no longer on its socket power cap; the ratio to `ms_per_step` is how much of the headline is clock, not schedule
+        zero_ctl = None
+        if world == 1 and not a.no_zero_control:
+            keep = {k: t.clone() for k, t in model._fused.items()}
+            for t_ in model._fused.values():
+                t_.zero_()
+            zl, zx0, zp, ze = latents.clone(), old_x0.clone(), prompt.clone(), emb.clone()
+            latents.zero_(); old_x0.zero_(); prompt.zero_(); emb.zero_()
+            znoise = torch.zeros(nf, 2, C, H, W, device=device, dtype=bf)
+
+            def zstep():
+                return worker.window_step(latents, old_x0, has_old, t, prev_t, next_t, znoise, grid_t, cond_t, emb)
+            zstep(); fence()
+            K.PROFILE.clear(); K.PROFILE_FILTER[0] = {ATTN}; K.PROFILE_ON[0] = True
+            zpow = PowerSampler(local_rank)
+            with zpow:
+                t1 = time.perf_counter()
+                for _ in range(3):
+                    zx = zstep()
+                fence()
+                zdt = time.perf_counter() - t1
+            K.PROFILE_ON[0] = False
+            zattn = K.profile_summary().get(ATTN, {"ms": float("nan"), "n": 0})
+            zero_ctl = {"what": "the same 3 window steps with every weight and every input zeroed (same launches, same schedules; timing only)", "steps": 3,
+                        "ms_per_step": 1e3 * zdt / 3, "attention_launch_ms": zattn["ms"], "finite": bool(torch.isfinite(zx[0]).all()), **zpow.summary()}
+            for k, t_ in model._fused.items():
+                t_.copy_(keep[k])
+            latents.copy_(zl); old_x0.copy_(zx0); prompt.copy_(zp); emb.copy_(ze)
+            del keep, zl, zx0, zp, ze
     rank_ms = [1e3 * dt / a.steps]
     if use_dist:
         mine = torch.tensor([dt], device=device, dtype=torch.float64)
@@ -918,6 +944,24 @@ def main():
         rank_ms = [1e3 * v / a.steps for v in every.tolist()]
         dt = float(every.max().item())
     if rank == 0:
+        # the headline: all a plain run computes and prints
+        line = {
+            "metric": "DiT denoising steps/sec, CogVideoX-5B To2V 720x480 (CFG-batched 13-frame FIFO window: DiT fwd + CFG + 13 DPM updates)",
+            # `value` is the WHOLE-JOB aggregate over the N ranks (the bench contract); BASELINE's metric is quoted per GPU: that is value_per_gpu.
+            # At N = 1 the two coincide.  Each rank runs a steady-state window (weak scaling); the end-to-end rate incl. the ramp is `--mode e2e`.
+            "value": world * a.steps / dt, "unit": "steps/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": 1e3 * dt / a.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "bf16", "data": "synthetic latents/embeddings, random-init weights at CogVideoX-5B shapes",
+            "config": {"workload": "To2V FIFO window step, CogVideoX-5B 42 layers D=3072, 226 text + 17550 video + 480 vip tokens, CFG batch 2, DPM-solver++",
+                       "layers": a.layers, "exchange": "RCCL all_gather of kept half-windows per step" if use_dist else "none"},
+            "value_aggregate": world * a.steps / dt, "value_per_gpu": a.steps / dt, "finite": finite,
+            "step_mfma_frac": FLOP_PER_STEP * (a.layers / 42.0) * (a.steps / dt) / PEAK_BF16,
+            "rank_ms_per_step": [round(v, 3) for v in rank_ms], "attn_path": attn_path,
+        }
+        if not a.full:
+            print(json.dumps(line))
+            sys.stdout.flush()
+    if rank == 0 and a.full:
         prof = all_prof
         attn = attn_prof
         attn_s = attn["ms"] * 1e-3
@@ -928,31 +972,21 @@ def main():
                 traffic = json.load(f)["_derived"]["attention_main_traffic_bytes_per_launch"]
         except (OSError, KeyError, ValueError):
             pass
-        out = {
-            "metric": "DiT denoising steps/sec, CogVideoX-5B To2V 720x480 (CFG-batched 13-frame FIFO window: DiT fwd + CFG + 13 DPM updates)",
-            # `value` is the WHOLE-JOB aggregate over the N ranks (the bench contract); BASELINE's metric is quoted per GPU: that is value_per_gpu.
-            # At N = 1 the two coincide.  Each rank runs a steady-state window (weak scaling); the end-to-end rate incl. the ramp is `--mode e2e`.
-            "value": world * a.steps / dt, "value_aggregate": world * a.steps / dt, "value_per_gpu": a.steps / dt, "value_is": "aggregate over n_gpus",
+        out = dict(line, **{
+            "value_is": "aggregate over n_gpus",
             "leg": "steady_state (one full window per rank per step; end to end incl. ramp / base stage / decode: --mode e2e, strong scaling)",
-            "unit": "steps/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": 1e3 * dt / a.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "bf16", "data": "synthetic latents/embeddings, random-init weights at CogVideoX-5B shapes",
-            "config": {"workload": "To2V FIFO window step, CogVideoX-5B 42 layers D=3072, 226 text + 17550 video + 480 vip tokens, CFG batch 2, DPM-solver++",
-                       "layers": a.layers, "exchange": "RCCL all_gather of kept half-windows per step" if use_dist else "none"},
-            "step_mfma_frac": FLOP_PER_STEP * (a.layers / 42.0) * (a.steps / dt) / PEAK_BF16,
             "roofline": {"bound": "mfma", "kernel": "attn_fwd_pp_kernel (tg_attention_fwd_multi: SDPA#1+#2 fused, SDPA#3 riding, key-split tail + combine)", "achieved": achieved,
                          "peak": PEAK_BF16 / 1e12, "unit": "TFLOP/s", "frac": achieved / (PEAK_BF16 / 1e12), "traffic": traffic,
                          "launch_ms": attn["ms"], "launches_timed": attn["n"], "attn_path": attn_path},
-            "attn_path": attn_path, "attn_retried_workgroups": retried, "finite": finite,
+            "attn_retried_workgroups": retried,
             "roofline_other_attn_path": {"attn_path": other, "launch_ms": other_prof["ms"], "launches_timed": other_prof["n"],
                                          "achieved": ATTN_FLOP_PER_LAUNCH / (other_prof["ms"] * 1e-3) / 1e12,
                                          "frac": ATTN_FLOP_PER_LAUNCH / (other_prof["ms"] * 1e-3) / PEAK_BF16, "step_ms_one_untimed_step": other_step_ms},
             "kernel_ms": {k: round(v["ms"], 4) for k, v in prof.items()},
-            "rank_ms_per_step": [round(v, 3) for v in rank_ms],
             # socket power and shader clock over the timed region (PowerSampler), top level so that the driver's record carries them
             "power_W_mean": power["power_W_mean"], "power_cap_W": power["power_cap_W"], "sclk_MHz_mean": power["sclk_MHz_mean"], "power": power,
             "zero_operand_control": zero_ctl,
-        }
+        })
         sclk = power["sclk_MHz_mean"]
         # the same achieved rates against the peak AT THE CLOCK THE CHIP ACTUALLY RAN (2.5 PF is quoted at 2400 MHz)
         out["roofline"]["frac_at_measured_clock"] = achieved / (PEAK_BF16 / 1e12 * sclk / 2400.0) if sclk else None

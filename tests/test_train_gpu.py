@@ -271,7 +271,7 @@ def test_attention_bwd_without_the_probe_flag_takes_two_launches():
 
 
 def test_attention_bwd_one_kernel_form_after_multi_stream_graph_work_in_a_child_process(golden_dir):
-    """bench.py's default run is window -> VAE (three tile streams + captured HIP graphs) -> training in ONE process, and after that VAE phase the
+    """bench.py --full runs window -> VAE (three tile streams + captured HIP graphs) -> training in ONE process, and after that VAE phase the
     dispatcher no longer puts workgroup b on XCD b % 8 (all 4096 probe workgroups were off it; residue classes still share an XCD).  The probe used to
     demand the identity and silently sent the training record to the two-launch form.  Child process: tiny tiled VAE decode / encode three times (eager,
     capture, replay), THEN the first backward call of the process — the device probe must pass, the one-kernel form must run, the gradients must match
