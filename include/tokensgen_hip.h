@@ -412,8 +412,8 @@ typedef struct tg_colsum_item {
 int tg_colsum_multi(const tg_colsum_item* items, int count, int row_blocks, float* partial, hipStream_t stream);
 
 /* Optimizer step on flat arenas (train_cogvideo_to2v.py:2012-2021: accelerator.clip_grad_norm_(transformer.parameters(), max_grad_norm), AdamW
- * (:1091-1098; betas / eps / weight decay of the yaml), zero_grad).  The reference's use_8bit_adam (bitsandbytes block-wise 8-bit moments, not under
- * /root/reference) exists to fit 80 GB parts; with 288 GB the moments stay fp32 (12.7 GB for the 1.6 B trainable parameters), which is torch.optim.AdamW.
+ * (:1091-1098; betas / eps / weight decay of the yaml), zero_grad).  tg_adamw_step keeps fp32 moments (torch.optim.AdamW); the yaml's
+ * use_8bit_adam (bitsandbytes AdamW8bit, block-wise 8-bit moments) is tg_adamw8bit_step below.
  *   tg_grad_accumulate: acc = (overwrite ? 0 : acc) + scale * grad   (grad bf16 or fp32; scale = 1 / gradient_accumulation_steps)
  *   tg_grad_clip_coef:  coef[0] = ||grad||_2 (fixed-order sum), coef[1] = min(1, max_norm / (coef[0] + 1e-6)); ws: tg_grad_norm_ws_floats() floats
  *   tg_adamw_step:      torch.optim.AdamW update of bf16 parameters with fp32 moments, gradient scaled by *clip_coef when given (device pointer,
@@ -433,6 +433,31 @@ long tg_grad_norm_ws_floats(void);
 int tg_grad_clip_coef(const float* grad, long n, float max_norm, float* ws, float* coef, hipStream_t stream);
 int tg_adamw_step(void* param, float* grad, float* exp_avg, float* exp_avg_sq, long n, int step, float lr, float beta1, float beta2, float eps,
                   float weight_decay, const float* clip_coef, int zero_grad, hipStream_t stream);
+
+/* Block-wise 8-bit AdamW (bitsandbytes 0.44.1 AdamW8bit, restated: DESIGN §8) over a whole arena in ONE launch, driven by a DEVICE-resident table of the
+ * arena's tensors (built once by the optimizer; rows in arena order, first_block ascending, first_block[0] == 0).  One workgroup per `block_size`
+ * elements of a tensor (block_size = 256 * {1, 2, 4, 8}; blocks restart at every tensor).
+ *   kind TG_ADAMW8BIT_BLOCKWISE: moments stored as uint8 codes in state1 / state2 at the tensor's ARENA offsets (arena-sized byte buffers), one fp32
+ *     absmax per block and moment in absmax1 / absmax2 from index `state`.  Per element: m = qmap1[code1] * absmax1[b], v = qmap2[code2] * absmax2[b]
+ *     -> the tg_adamw_step arithmetic in fp32 (the parameter takes the UNQUANTISED m, v) -> absmax = max |m| (|v|) over the block's elements ->
+ *     code = nearest entry of the sorted 256-entry map to m * (1 / absmax) (ties to the lower code; a non-zero m whose code has the other sign moves one
+ *     code towards it); an all-zero block stores absmax 0 and the code of 0.0.
+ *   kind TG_ADAMW8BIT_FP32: fp32 moments in small_m / small_v from element `state` (compact side arena), exactly the tg_adamw_step update.
+ * clipped != 0: the gradient is scaled by *clip_coef (device pointer, may be NULL = 1).  qmap1 (signed) / qmap2 (unsigned): 256 ascending fp32 each,
+ * device memory.  Arena padding past a tensor's numel is never written.  Deterministic: no atomics, no order-dependent sums. */
+#define TG_ADAMW8BIT_FP32 0
+#define TG_ADAMW8BIT_BLOCKWISE 1
+typedef struct tg_adamw8bit_row {
+    long offset;                 /* first arena element of the tensor */
+    long numel;
+    long state;                  /* BLOCKWISE: index of the tensor's first block in absmax1 / absmax2; FP32: first element in small_m / small_v */
+    long first_block;            /* workgroups of the earlier rows */
+    int  kind;
+    int  clipped;
+} tg_adamw8bit_row;
+int tg_adamw8bit_step(void* param, float* grad, uint8_t* state1, uint8_t* state2, float* absmax1, float* absmax2, float* small_m, float* small_v,
+                      const float* qmap1, const float* qmap2, const tg_adamw8bit_row* rows, int nrows, long nblocks, int block_size, int step,
+                      float lr, float beta1, float beta2, float eps, float weight_decay, const float* clip_coef, int zero_grad, hipStream_t stream);
 
 /* Training loss of the To2V step and its gradient w.r.t. the model output (train_cogvideo_to2v.py:1995-2004; get_velocity
  * scheduling_dpm_cogvideox.py:521-538), per frame f (per-frame timesteps) over frame_elems elements:

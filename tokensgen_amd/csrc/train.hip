@@ -690,6 +690,138 @@ __global__ __launch_bounds__(OPT_BLOCK) void adamw_kernel(bf16_t* __restrict__ p
     }
 }
 
+// Block-wise 8-bit AdamW (header: tg_adamw8bit_step).  One 256-lane workgroup per quantisation block of OPT_BLOCK * EPL elements, EPL contiguous
+// elements per lane (16-byte bf16 / 2 x 16-byte fp32 / 8-byte code accesses at EPL = 8).  The workgroup finds its tensor by a binary search over the
+// table's first_block (the same index in every lane: scalar loads).  A lane whose chunk starts inside the tensor reads its whole chunk: the chunk ends
+// inside the tensor's 64-element-aligned arena slot, so the tail lane's extra elements are padding that is read, masked out and never written.
+template <int EPL>
+struct Chunk {
+    typedef __attribute__((ext_vector_type(EPL))) float f;
+    typedef __attribute__((ext_vector_type(EPL))) unsigned short h;
+    typedef __attribute__((ext_vector_type(EPL))) unsigned char b;
+};
+
+// index of the nearest entry of the ascending 256-entry map q to x (ties: the lower index)
+__device__ __forceinline__ int quantize_nearest(const float* q, float x) {
+    int j = 0;
+#pragma unroll
+    for (int s = 128; s > 0; s >>= 1)
+        if (q[j + s] <= x) j += s;                  // j = largest index with q[j] <= x (0 when x < q[0])
+    j = j < 254 ? j : 254;
+    return (q[j + 1] - x) < (x - q[j]) ? j + 1 : j;
+}
+
+template <int EPL>
+__global__ __launch_bounds__(OPT_BLOCK) void adamw8bit_kernel(bf16_t* __restrict__ p, float* __restrict__ g, uint8_t* __restrict__ s1, uint8_t* __restrict__ s2,
+                                                              float* __restrict__ amax1, float* __restrict__ amax2, float* __restrict__ sm, float* __restrict__ sv,
+                                                              const float* __restrict__ qmap1, const float* __restrict__ qmap2,
+                                                              const tg_adamw8bit_row* __restrict__ rows, int nrows, float lr, float b1, float b2, float eps, float wd,
+                                                              float bc1, float bc2_sqrt, const float* __restrict__ clip, int zero_grad) {
+    typedef typename Chunk<EPL>::f fv;
+    typedef typename Chunk<EPL>::h hv;
+    typedef typename Chunk<EPL>::b bv;
+    __shared__ float q1[256], q2[256];
+    __shared__ float red[2][OPT_BLOCK / 64];
+    const int tid = threadIdx.x;
+    q1[tid] = qmap1[tid];                                      // OPT_BLOCK == 256 == map entries
+    q2[tid] = qmap2[tid];
+    int lo = 0, hi = nrows;                                    // rows[lo].first_block <= blockIdx.x < rows[hi].first_block
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((long)blockIdx.x >= rows[mid].first_block) lo = mid; else hi = mid;
+    }
+    const long off = rows[lo].offset, n = rows[lo].numel, st = rows[lo].state, blk = (long)blockIdx.x - rows[lo].first_block;
+    const int kind = rows[lo].kind;
+    const float cs = (rows[lo].clipped && clip) ? *clip : 1.f;
+    const long e0 = blk * (OPT_BLOCK * EPL) + (long)tid * EPL;   // first element of this lane's chunk, inside the tensor
+    const int nv = e0 < n ? (n - e0 < EPL ? (int)(n - e0) : EPL) : 0;
+    const long a = off + e0;                                   // its arena index
+    float pf[EPL] = {}, gf[EPL] = {}, mf[EPL], vf[EPL];
+    if (nv > 0) {
+        const hv ph = *reinterpret_cast<const hv*>(p + a);
+        const fv gg = *reinterpret_cast<const fv*>(g + a);
+#pragma unroll
+        for (int k = 0; k < EPL; ++k) { pf[k] = bf16_to_f32(ph[k]); gf[k] = gg[k]; }
+    }
+    if (kind == TG_ADAMW8BIT_FP32) {                           // uniform over the workgroup: no barrier below is skipped by part of it
+        if (nv == 0) return;
+        const fv mm = *reinterpret_cast<const fv*>(sm + st + e0), vv = *reinterpret_cast<const fv*>(sv + st + e0);
+#pragma unroll
+        for (int k = 0; k < EPL; ++k) { mf[k] = mm[k]; vf[k] = vv[k]; }
+    } else {
+        bv c1 = {}, c2 = {};
+        if (nv > 0) { c1 = *reinterpret_cast<const bv*>(s1 + a); c2 = *reinterpret_cast<const bv*>(s2 + a); }
+        const float am1 = amax1[st + blk], am2 = amax2[st + blk];
+        __syncthreads();                                       // maps in LDS
+#pragma unroll
+        for (int k = 0; k < EPL; ++k) { mf[k] = q1[c1[k]] * am1; vf[k] = q2[c2[k]] * am2; }
+    }
+    // the tg_adamw_step arithmetic (adamw_kernel), fp32
+#pragma unroll
+    for (int k = 0; k < EPL; ++k) {
+        const float gi = gf[k] * cs;
+        float pi = pf[k];
+        pi *= 1.f - lr * wd;
+        const float mi = b1 * mf[k] + (1.f - b1) * gi;
+        const float vi = b2 * vf[k] + (1.f - b2) * gi * gi;
+        mf[k] = mi; vf[k] = vi;
+        const float denom = sqrtf(vi) / bc2_sqrt + eps;
+        pi -= (lr / bc1) * (mi / denom);
+        pf[k] = pi;
+    }
+    if (kind == TG_ADAMW8BIT_FP32) {
+        if (nv == EPL) {
+            fv mm, vv;
+#pragma unroll
+            for (int k = 0; k < EPL; ++k) { mm[k] = mf[k]; vv[k] = vf[k]; }
+            *reinterpret_cast<fv*>(sm + st + e0) = mm;
+            *reinterpret_cast<fv*>(sv + st + e0) = vv;
+        } else {
+            for (int k = 0; k < nv; ++k) { sm[st + e0 + k] = mf[k]; sv[st + e0 + k] = vf[k]; }
+        }
+    } else {
+        float x1 = 0.f, x2 = 0.f;                              // new absmax over the block's valid elements
+#pragma unroll
+        for (int k = 0; k < EPL; ++k)
+            if (k < nv) { x1 = fmaxf(x1, fabsf(mf[k])); x2 = fmaxf(x2, fabsf(vf[k])); }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { x1 = fmaxf(x1, __shfl_xor(x1, o, 64)); x2 = fmaxf(x2, __shfl_xor(x2, o, 64)); }
+        if ((tid & 63) == 0) { red[0][tid >> 6] = x1; red[1][tid >> 6] = x2; }
+        __syncthreads();
+        x1 = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
+        x2 = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
+        if (tid == 0) { amax1[st + blk] = x1; amax2[st + blk] = x2; }
+        const float r1 = x1 > 0.f ? 1.f / x1 : 0.f, r2 = x2 > 0.f ? 1.f / x2 : 0.f;   // all-zero block: every element maps to 0.0
+        bv c1, c2;
+#pragma unroll
+        for (int k = 0; k < EPL; ++k) {
+            int c = quantize_nearest(q1, mf[k] * r1);
+            if (mf[k] != 0.f && signbit(q1[c]) != signbit(mf[k])) c += mf[k] > 0.f ? 1 : -1;   // keep the sign of m (bitsandbytes)
+            c1[k] = (unsigned char)c;
+            c2[k] = (unsigned char)quantize_nearest(q2, vf[k] * r2);
+        }
+        if (nv == EPL) {
+            *reinterpret_cast<bv*>(s1 + a) = c1;
+            *reinterpret_cast<bv*>(s2 + a) = c2;
+        } else {
+            for (int k = 0; k < nv; ++k) { s1[a + k] = c1[k]; s2[a + k] = c2[k]; }
+        }
+    }
+    if (nv == EPL) {
+        hv ph;
+        fv z = {};
+#pragma unroll
+        for (int k = 0; k < EPL; ++k) ph[k] = f32_to_bf16(pf[k]);
+        *reinterpret_cast<hv*>(p + a) = ph;
+        if (zero_grad) *reinterpret_cast<fv*>(g + a) = z;
+    } else {
+        for (int k = 0; k < nv; ++k) {
+            p[a + k] = f32_to_bf16(pf[k]);
+            if (zero_grad) g[a + k] = 0.f;
+        }
+    }
+}
+
 inline unsigned opt_blocks(long n) { const long b = (n + OPT_BLOCK - 1) / OPT_BLOCK; return (unsigned)(b < OPT_MAX_BLOCKS ? (b > 0 ? b : 1) : OPT_MAX_BLOCKS); }
 }  // namespace
 
@@ -745,5 +877,31 @@ extern "C" int tg_adamw_step(void* param, float* grad, float* exp_avg, float* ex
     hipLaunchKernelGGL(adamw_kernel, dim3(opt_blocks(n)), dim3(OPT_BLOCK), 0, stream, (bf16_t*)param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps,
                        weight_decay, bc1, bc2s, clip_coef, zero_grad);
     TG_LAUNCH_CHECK("tg_adamw_step");
+    return TG_OK;
+}
+
+extern "C" int tg_adamw8bit_step(void* param, float* grad, uint8_t* state1, uint8_t* state2, float* absmax1, float* absmax2, float* small_m, float* small_v,
+                                 const float* qmap1, const float* qmap2, const tg_adamw8bit_row* rows, int nrows, long nblocks, int block_size, int step,
+                                 float lr, float beta1, float beta2, float eps, float weight_decay, const float* clip_coef, int zero_grad, hipStream_t stream) {
+    TG_REQUIRE(param && grad && state1 && state2 && absmax1 && absmax2 && small_m && small_v && qmap1 && qmap2 && rows, TG_ERR_ARG,
+               "tg_adamw8bit_step: null pointer");
+    TG_REQUIRE(nrows > 0 && nblocks > 0 && step >= 1, TG_ERR_SHAPE, "tg_adamw8bit_step: nrows, nblocks and step must be positive");
+    TG_REQUIRE(nblocks < (1L << 31), TG_ERR_SHAPE, "tg_adamw8bit_step: %ld workgroups", nblocks);
+    TG_REQUIRE(block_size == OPT_BLOCK || block_size == 2 * OPT_BLOCK || block_size == 4 * OPT_BLOCK || block_size == 8 * OPT_BLOCK, TG_ERR_SHAPE,
+               "tg_adamw8bit_step: block_size %d not in {256, 512, 1024, 2048}", block_size);
+    TG_REQUIRE(tg_aligned16(param) && tg_aligned16(grad) && tg_aligned16(state1) && tg_aligned16(state2) && tg_aligned16(small_m) && tg_aligned16(small_v),
+               TG_ERR_ALIGN, "tg_adamw8bit_step: arenas must be 16-byte aligned");
+    const float bc1 = 1.f - powf(beta1, (float)step), bc2s = sqrtf(1.f - powf(beta2, (float)step));
+#define TG_ADAM8_LAUNCH(E)                                                                                                                          \
+    hipLaunchKernelGGL(adamw8bit_kernel<E>, dim3((unsigned)nblocks), dim3(OPT_BLOCK), 0, stream, (bf16_t*)param, grad, state1, state2, absmax1, absmax2, \
+                       small_m, small_v, qmap1, qmap2, rows, nrows, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, clip_coef, zero_grad)
+    switch (block_size / OPT_BLOCK) {
+        case 1: TG_ADAM8_LAUNCH(1); break;
+        case 2: TG_ADAM8_LAUNCH(2); break;
+        case 4: TG_ADAM8_LAUNCH(4); break;
+        default: TG_ADAM8_LAUNCH(8); break;
+    }
+#undef TG_ADAM8_LAUNCH
+    TG_LAUNCH_CHECK("tg_adamw8bit_step");
     return TG_OK;
 }

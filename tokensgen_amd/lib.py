@@ -54,6 +54,7 @@ PROTOTYPES = {
     "tg_grad_accumulate": [_vp, _i, _vp, _l, _f, _i, _vp],
     "tg_grad_clip_coef": [_vp, _l, _f, _vp, _vp, _vp],
     "tg_adamw_step": [_vp, _vp, _vp, _vp, _l, _i, _f, _f, _f, _f, _f, _vp, _i, _vp],
+    "tg_adamw8bit_step": [_vp] * 11 + [_i, _l, _i, _i, _f, _f, _f, _f, _f, _vp, _i, _vp],
     "tg_vpred_loss_grad": [_vp, _vp, _vp, _vp, _i, _l, _f, _vp, _vp, _vp],
     "tg_timestep_sinusoid": [_vp, _i, _i, _vp, _vp],
     "tg_rope_table_3d": [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp],
@@ -183,6 +184,14 @@ class ColsumItem(C.Structure):
 
 
 TG_ACCUM_MAX, TG_COLSUM_MAX = 48, 16
+
+
+class Adamw8bitRow(C.Structure):
+    """tg_adamw8bit_row (include/tokensgen_hip.h)"""
+    _fields_ = [("offset", C.c_long), ("numel", C.c_long), ("state", C.c_long), ("first_block", C.c_long), ("kind", C.c_int), ("clipped", C.c_int)]
+
+
+ADAMW8BIT_FP32, ADAMW8BIT_BLOCKWISE = 0, 1
 
 
 class AttnSegment(C.Structure):

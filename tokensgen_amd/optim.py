@@ -1,11 +1,15 @@
-"""Optimizer side of the To2V training step (train_cogvideo_to2v.py:1083-1098 optimizer, :1157-1164 DDP, :1726 accumulate,
+"""Optimizer side of the To2V training step (train_cogvideo_to2v.py:1056-1130 optimizer, :1157-1164 DDP, :1726 accumulate,
 :2012-2021 clip / step / zero_grad).
 
 MI355X-first layout: every trainable parameter lives in ONE flat bf16 arena (the state-dict entries the kernels read are views of it), with one
-flat fp32 arena each for the accumulated gradient and the two AdamW moments.  The optimizer step is then three streaming launches over the arena
+flat fp32 arena for the accumulated gradient and the optimizer state beside it.  The optimizer step is then three streaming launches over the arena
 (sum of squares -> clip coefficient on the device -> AdamW + zero_grad), and the data-parallel gradient exchange is a handful of large RCCL
 all-reduces over slices of the same buffer (xGMI rings are per-link bound: few big buckets, once per `gradient_accumulation_steps` micro-steps —
-the reference's `no_sync` for the other eight).  288 GB of HBM is why the moments are fp32 instead of bitsandbytes' 8-bit blocks."""
+the reference's `no_sync` for the other eight).  Two optimizers: `AdamW` keeps fp32 moments (torch.optim.AdamW); `AdamW8bit` is the yaml's
+`use_8bit_adam: true` (bitsandbytes AdamW8bit): block-wise 8-bit moments, 2 B per parameter instead of 8, on an arena built with `moments=False`.
+`get_optimizer` picks one from the yaml's keys."""
+import warnings
+
 import torch
 
 from . import kernels as K
@@ -37,9 +41,10 @@ def arena_order(names, num_layers):
 
 class ParamArena:
     """Flat storage for the trainable parameters.  `params`: {name: tensor}; `order`: names in arena order.  After construction `views[name]` is a
-    bf16 view of the arena holding the parameter (install these in the state dict the kernels use)."""
+    bf16 view of the arena holding the parameter (install these in the state dict the kernels use).  moments=False: no fp32 moment arenas
+    (exp_avg / exp_avg_sq are None) — the arena of an AdamW8bit, which keeps its own 8-bit state."""
 
-    def __init__(self, params, order, device):
+    def __init__(self, params, order, device, moments=True):
         self.names = list(order)
         self.offsets, self.shapes = {}, {}
         off = 0
@@ -49,8 +54,8 @@ class ParamArena:
         self.numel = off
         self.param = torch.zeros(off, dtype=BF16, device=device)
         self.grad = torch.zeros(off, dtype=torch.float32, device=device)
-        self.exp_avg = torch.zeros(off, dtype=torch.float32, device=device)
-        self.exp_avg_sq = torch.zeros(off, dtype=torch.float32, device=device)
+        self.exp_avg = torch.zeros(off, dtype=torch.float32, device=device) if moments else None
+        self.exp_avg_sq = torch.zeros(off, dtype=torch.float32, device=device) if moments else None
         self.views = {}
         for n in self.names:
             v = self.param[self.offsets[n]: self.offsets[n] + params[n].numel()].view(self.shapes[n])
@@ -113,6 +118,8 @@ class AdamW:
     global L2 norm; the rest (the Resampler) is stepped unclipped, as in the reference."""
 
     def __init__(self, arena, lr=2e-4, betas=(0.9, 0.95), eps=1e-8, weight_decay=1e-4, max_grad_norm=1.0, clip_elems=None):
+        if arena.exp_avg is None:
+            raise ValueError("AdamW needs a ParamArena with fp32 moments (moments=True); an arena built with moments=False is for AdamW8bit")
         self.arena, self.lr, self.betas, self.eps, self.wd, self.max_norm = arena, lr, betas, eps, weight_decay, max_grad_norm
         self.clip_elems = arena.numel if clip_elems is None else int(clip_elems)
         self.t = 0
@@ -153,6 +160,9 @@ class AdamW:
     @torch.no_grad()
     def load_state_dict(self, sd):
         a = self.arena
+        kind = sd.get("hyper", {}).get("kind", "adamw")
+        if kind != "adamw":
+            raise ValueError(f"AdamW.load_state_dict: the checkpoint holds {kind!r} optimizer state, not fp32 AdamW moments")
         if [(n, int(o), tuple(sh)) for n, o, sh in sd["layout"]] != a.layout():
             raise ValueError("AdamW.load_state_dict: the checkpoint's arena layout (names / offsets / shapes) differs from this arena's")
         for name in ("exp_avg", "exp_avg_sq", "grad"):
@@ -164,6 +174,174 @@ class AdamW:
         h = sd.get("hyper", {})
         self.lr, self.betas, self.eps = h.get("lr", self.lr), tuple(h.get("betas", self.betas)), h.get("eps", self.eps)
         self.wd, self.max_norm, self.clip_elems = h.get("weight_decay", self.wd), h.get("max_grad_norm", self.max_norm), int(h.get("clip_elems", self.clip_elems))
+
+
+def dynamic_map(signed=True, max_exponent_bits=7, total_bits=8):
+    """bitsandbytes.functional.create_dynamic_map (0.44.1), restated in the same torch fp32 operations: for every decade e = 0 .. max_exponent_bits-1
+    the means of linearly spaced fractions in [0.1, 1] scaled by 10^(e - max_exponent_bits + 1) (and their negatives if signed), plus 0 and 1.0; the
+    256 codes sorted ascending.  AdamW8bit quantises exp_avg with the signed map and exp_avg_sq with the unsigned one."""
+    non_sign_bits = total_bits - 1                         # bitsandbytes: `total_bits - (1 if signed else 1)`
+    if 2 ** (non_sign_bits - max_exponent_bits) - 1 != 0:
+        raise NotImplementedError("dynamic_map: only the layouts without extra zero-exponent items (AdamW8bit's 7 exponent bits of 8)")
+    data = []
+    for i in range(max_exponent_bits):
+        items = 2 ** (i + non_sign_bits - max_exponent_bits) + 1 if signed else 2 ** (i + non_sign_bits - max_exponent_bits + 1) + 1
+        bounds = torch.linspace(0.1, 1, items)
+        means = (bounds[:-1] + bounds[1:]) / 2.0
+        data += ((10 ** (-(max_exponent_bits - 1) + i)) * means).tolist()
+        if signed:
+            data += (-(10 ** (-(max_exponent_bits - 1) + i)) * means).tolist()
+    data += [0.0, 1.0]
+    assert len(data) == 2 ** total_bits
+    data.sort()
+    return torch.tensor(data, dtype=torch.float32)
+
+
+class BlockRow:
+    """One row of the AdamW8bit tensor table (tg_adamw8bit_row): `kind` L.ADAMW8BIT_BLOCKWISE or L.ADAMW8BIT_FP32, `state` = first absmax index or
+    first element in the small fp32 moment arenas, `first_block` = workgroups of the earlier rows, `blocks` = this tensor's."""
+    __slots__ = ("name", "offset", "numel", "kind", "state", "first_block", "blocks", "clipped")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+def block_table(arena, block_size=2048, min_8bit_size=4096, clip_elems=None):
+    """The static tensor table of AdamW8bit over `arena` (arena order): returns (rows, absmax entries per moment, small fp32 moment elements).
+    Tensors with numel >= min_8bit_size get 8-bit moments in blocks of block_size that restart at the tensor's first element (the last may be
+    partial); the others keep fp32 moments in a compact side arena (64-element aligned slots).  clipped: the tensor lies below clip_elems."""
+    clip_elems = arena.numel if clip_elems is None else int(clip_elems)
+    rows, n_absmax, n_small, wg = [], 0, 0, 0
+    for n in arena.names:
+        off, k = arena.offsets[n], arena.views[n].numel()
+        if off < clip_elems < off + k:
+            raise ValueError(f"AdamW8bit: clip_elems {clip_elems} splits the tensor {n} [{off}, {off + k}); it must fall on a tensor boundary")
+        blocks = (k + block_size - 1) // block_size
+        if k >= min_8bit_size:
+            rows.append(BlockRow(name=n, offset=off, numel=k, kind=L.ADAMW8BIT_BLOCKWISE, state=n_absmax, first_block=wg, blocks=blocks, clipped=off < clip_elems))
+            n_absmax += blocks
+        else:
+            rows.append(BlockRow(name=n, offset=off, numel=k, kind=L.ADAMW8BIT_FP32, state=n_small, first_block=wg, blocks=blocks, clipped=off < clip_elems))
+            n_small += (k + _ALIGN - 1) // _ALIGN * _ALIGN
+        wg += blocks
+    return rows, n_absmax, n_small
+
+
+class AdamW8bit:
+    """bitsandbytes AdamW8bit (0.44.1, block-wise; the yaml's `use_8bit_adam: true`, train_cogvideo_to2v.py:1083-1098) on a ParamArena, with the
+    same surface as AdamW (step / coef / t / state_dict / load_state_dict) and the same clipping split.  Tensors of >= min_8bit_size elements keep
+    both moments as uint8 codes of the dynamic maps (exp_avg signed, exp_avg_sq unsigned) in blocks of block_size elements with one fp32 absmax per
+    block and moment; the state arenas are byte arenas at the parameter arena's offsets.  Smaller tensors keep fp32 moments.  The update itself is
+    tg_adamw_step's fp32 arithmetic on the dequantised moments (where this restates bitsandbytes).  Build the arena with moments=False:
+    the fp32 moment arenas are what this optimizer saves."""
+
+    KIND = "adamw8bit"
+
+    def __init__(self, arena, lr=2e-4, betas=(0.9, 0.95), eps=1e-8, weight_decay=1e-4, max_grad_norm=1.0, clip_elems=None, min_8bit_size=4096,
+                 block_size=2048):
+        if block_size not in (256, 512, 1024, 2048):
+            raise ValueError(f"AdamW8bit: block_size {block_size} not in (256, 512, 1024, 2048)")
+        self.arena, self.lr, self.betas, self.eps, self.wd, self.max_norm = arena, lr, tuple(betas), eps, weight_decay, max_grad_norm
+        self.clip_elems = arena.numel if clip_elems is None else int(clip_elems)
+        self.min_8bit_size, self.block_size = int(min_8bit_size), int(block_size)
+        self.t = 0
+        dev = arena.param.device
+        self.rows, n_absmax, n_small = block_table(arena, self.block_size, self.min_8bit_size, self.clip_elems)
+        self.nblocks = self.rows[-1].first_block + self.rows[-1].blocks
+        self.state1 = torch.zeros(arena.numel, dtype=torch.uint8, device=dev)          # codes start at 0 with absmax 0: the moments dequantise to 0
+        self.state2 = torch.zeros(arena.numel, dtype=torch.uint8, device=dev)
+        self.absmax1 = torch.zeros(max(n_absmax, 1), dtype=torch.float32, device=dev)
+        self.absmax2 = torch.zeros(max(n_absmax, 1), dtype=torch.float32, device=dev)
+        self.small_m = torch.zeros(max(n_small, _ALIGN), dtype=torch.float32, device=dev)
+        self.small_v = torch.zeros(max(n_small, _ALIGN), dtype=torch.float32, device=dev)
+        self.qmap1, self.qmap2 = dynamic_map(True).to(dev), dynamic_map(False).to(dev)
+        tab = (L.Adamw8bitRow * len(self.rows))()
+        for i, r in enumerate(self.rows):
+            tab[i].offset, tab[i].numel, tab[i].state, tab[i].first_block, tab[i].kind, tab[i].clipped = r.offset, r.numel, r.state, r.first_block, r.kind, int(r.clipped)
+        self._table = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)   # device-resident, built once: the layout is static
+        self._ws = torch.empty(L.load().tg_grad_norm_ws_floats(), dtype=torch.float32, device=dev)
+        self.coef = torch.ones(2, dtype=torch.float32, device=dev)        # [total norm, clip coefficient] of the last step (device side)
+
+    @torch.no_grad()
+    def step(self, lr=None, zero_grad=True):
+        a, lib = self.arena, L.load()
+        self.t += 1
+        lr = self.lr if lr is None else lr
+        st = K._stream()
+        clip_ptr = None
+        nc = self.clip_elems
+        if self.max_norm is not None and self.max_norm > 0 and nc > 0:
+            L.check(lib.tg_grad_clip_coef(a.grad.data_ptr(), nc, float(self.max_norm), self._ws.data_ptr(), self.coef.data_ptr(), st), "tg_grad_clip_coef")
+            clip_ptr = self.coef.data_ptr() + 4
+        L.check(lib.tg_adamw8bit_step(a.param.data_ptr(), a.grad.data_ptr(), self.state1.data_ptr(), self.state2.data_ptr(), self.absmax1.data_ptr(),
+                                      self.absmax2.data_ptr(), self.small_m.data_ptr(), self.small_v.data_ptr(), self.qmap1.data_ptr(), self.qmap2.data_ptr(),
+                                      self._table.data_ptr(), len(self.rows), self.nblocks, self.block_size, self.t, float(lr), float(self.betas[0]),
+                                      float(self.betas[1]), float(self.eps), float(self.wd), clip_ptr, 1 if zero_grad else 0, st), "tg_adamw8bit_step")
+
+    # ---- checkpoint / resume, as AdamW: {"t", "state1" / "state2": the uint8 code arenas, "absmax1" / "absmax2", "small_m" / "small_v": the fp32
+    # moments of the small tensors, "grad", "layout", "hyper": AdamW's keys + kind / block_size / min_8bit_size}
+    _STATE = ("state1", "state2", "absmax1", "absmax2", "small_m", "small_v")
+
+    def state_dict(self):
+        a = self.arena
+        sd = {"t": int(self.t), "grad": a.grad.detach().cpu().clone(), "layout": a.layout(),
+              "hyper": {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd, "max_grad_norm": self.max_norm,
+                        "clip_elems": self.clip_elems, "kind": self.KIND, "block_size": self.block_size, "min_8bit_size": self.min_8bit_size}}
+        for name in self._STATE:
+            sd[name] = getattr(self, name).detach().cpu().clone()
+        return sd
+
+    @torch.no_grad()
+    def load_state_dict(self, sd):
+        a = self.arena
+        h = sd.get("hyper", {})
+        kind = h.get("kind", "adamw")
+        if kind != self.KIND:
+            raise ValueError(f"AdamW8bit.load_state_dict: the checkpoint holds {kind!r} optimizer state, not {self.KIND!r}")
+        for key, mine in (("block_size", self.block_size), ("min_8bit_size", self.min_8bit_size)):
+            if int(h.get(key, -1)) != mine:
+                raise ValueError(f"AdamW8bit.load_state_dict: the checkpoint's {key} is {h.get(key)}, this optimizer's is {mine}")
+        if [(n, int(o), tuple(sh)) for n, o, sh in sd["layout"]] != a.layout():
+            raise ValueError("AdamW8bit.load_state_dict: the checkpoint's arena layout (names / offsets / shapes) differs from this arena's")
+        for name in self._STATE + ("grad",):
+            dst = a.grad if name == "grad" else getattr(self, name)
+            t = sd[name]
+            if t.numel() != dst.numel() or t.dtype != dst.dtype:
+                raise ValueError(f"AdamW8bit.load_state_dict: {name} has {t.numel()} {t.dtype} elements, this optimizer has {dst.numel()} {dst.dtype}")
+            dst.copy_(t.to(dst.device))
+        self.t = int(sd["t"])
+        self.lr, self.betas, self.eps = h.get("lr", self.lr), tuple(h.get("betas", self.betas)), h.get("eps", self.eps)
+        self.wd, self.max_norm = h.get("weight_decay", self.wd), h.get("max_grad_norm", self.max_norm)
+        if int(h.get("clip_elems", self.clip_elems)) != self.clip_elems:
+            raise ValueError(f"AdamW8bit.load_state_dict: the checkpoint's clip_elems is {h.get('clip_elems')}, this optimizer's is {self.clip_elems} "
+                             "(the table's clipped flags are fixed at construction)")
+
+
+def get_optimizer(arena, cfg, clip_elems=None):
+    """The reference's get_optimizer (train_cogvideo_to2v.py:1056-1130) for its yaml keys: optimizer, use_8bit_adam, learning_rate, adam_beta1 /
+    adam_beta2, adam_epsilon, adam_weight_decay, max_grad_norm (argparse defaults where a key is missing).  `cfg`: a dict or an object with those
+    attributes.  "adamw" -> AdamW, "adamw" + use_8bit_adam -> AdamW8bit (build the arena with moments=False); use_8bit_adam with another optimizer is
+    ignored with a warning, an unknown optimizer falls back to "adamw" with a warning; "adam" and "prodigy" raise NotImplementedError."""
+    get = cfg.get if isinstance(cfg, dict) else (lambda k, d=None: getattr(cfg, k, d))
+    name = str(get("optimizer", "adam")).lower()
+    if name not in ("adam", "adamw", "prodigy"):
+        warnings.warn(f"Unsupported choice of optimizer: {name}. Supported optimizers include ['adam', 'adamw', 'prodigy']. Defaulting to AdamW")
+        name = "adamw"
+    use_8bit = bool(get("use_8bit_adam", False))
+    if use_8bit and name not in ("adam", "adamw"):
+        warnings.warn(f"use_8bit_adam is ignored when optimizer is not set to 'Adam' or 'AdamW'. Optimizer was set to {name}")
+        use_8bit = False
+    if name == "adam":
+        raise NotImplementedError("optimizer 'adam' (torch.optim.Adam / bitsandbytes Adam8bit: weight decay added to the gradient) is not implemented; "
+                                  "the training yamls use 'adamw'")
+    if name == "prodigy":
+        raise NotImplementedError("optimizer 'prodigy' (prodigyopt.Prodigy: learning-rate-free D-adaptation) is not implemented; the training yamls "
+                                  "use 'adamw'")
+    kw = dict(lr=float(get("learning_rate", 1e-4)), betas=(float(get("adam_beta1", 0.9)), float(get("adam_beta2", 0.95))),
+              eps=float(get("adam_epsilon", 1e-8)), weight_decay=float(get("adam_weight_decay", 1e-4)), max_grad_norm=float(get("max_grad_norm", 1.0)),
+              clip_elems=clip_elems)
+    return AdamW8bit(arena, **kw) if use_8bit else AdamW(arena, **kw)
 
 
 def constant_with_warmup(step, base_lr, warmup_steps):

@@ -1,0 +1,92 @@
+"""Optimizer step at the full To2V trainable layout (42 layers of vip_ tensors + the Resampler, 1.97 B parameters): optim.AdamW (fp32 moments) against
+optim.AdamW8bit (block-wise 8-bit moments) in the same process, alternating, timed with device events.  Each step = clip coefficient (one read of
+the clipped gradient) + the AdamW launch; algorithmic bytes of the AdamW pass: 28 B / element fp32 (bf16 parameter read + write, fp32 gradient
+read + zero, both fp32 moments read + written), 16 B / element 8-bit (the moments as 1-byte codes).  Also the optimizer-state memory of both,
+measured as torch.cuda.memory_allocated deltas.  Prints one JSON line; `--out PATH` also writes it to a file (the committed record is
+profiles/r7_optim_step.json)."""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+HBM = 8.0e12          # MI355X HBM3E peak, bytes / s
+
+
+def layout_params(dev):
+    import bench
+    model = bench.build_model(dev, 42)
+    sd = {k: v.detach() for k, v in model.state_dict().items()}
+    params = {k: sd[k] for k in sorted(k for k in sd if "vip_" in k)}
+    rsd, _, _ = bench.build_resampler_sd(dev)
+    params.update({"resampler." + k: v for k, v in rsd.items()})
+    return model, params
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    a = ap.parse_args()
+    from tokensgen_amd import optim
+    dev = "cuda"
+    model, params = layout_params(dev)
+    n_params = sum(v.numel() for v in params.values())
+    order = optim.arena_order(list(params), 42)
+    m0 = torch.cuda.memory_allocated()
+    a32 = optim.ParamArena(params, order, dev)
+    m1 = torch.cuda.memory_allocated()
+    a8 = optim.ParamArena(params, order, dev, moments=False)
+    m2 = torch.cuda.memory_allocated()
+    del model, params
+    torch.cuda.empty_cache()
+    n_clip = a32.prefix_elems(lambda n: not n.startswith("resampler."))
+    hyper = dict(lr=2e-4, betas=(0.9, 0.95), eps=1e-8, weight_decay=1e-4, max_grad_norm=1.0, clip_elems=n_clip)
+    opt32 = optim.AdamW(a32, **hyper)
+    m3 = torch.cuda.memory_allocated()
+    opt8 = optim.AdamW8bit(a8, **hyper)
+    torch.cuda.synchronize()
+    m4 = torch.cuda.memory_allocated()
+    state32 = (m1 - m0) - (m2 - m1)                 # the two fp32 moment arenas: what moments=False leaves out
+    state8 = m4 - m3
+    gen = torch.Generator(device=dev).manual_seed(3)
+    grad = torch.zeros_like(a32.grad)
+    for n in a32.names:
+        v = a32.grad_view(n)
+        grad[a32.offsets[n]:a32.offsets[n] + v.numel()].normal_(generator=gen).mul_(1e-5)
+    runs = {"adamw_fp32": (a32, opt32, 28), "adamw_8bit": (a8, opt8, 16)}
+    ms = {k: [] for k in runs}
+    for r in range(a.rounds + 1):                    # round 0: warm-up (code objects, first touch)
+        for name, (arena, opt, _) in runs.items():
+            arena.grad.copy_(grad)
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            opt.step()
+            e1.record()
+            torch.cuda.synchronize()
+            if r:
+                ms[name].append(e0.elapsed_time(e1))
+    rec = {"what": "optimizer step at the full To2V trainable layout (clip coefficient + AdamW pass), device events, alternating",
+           "params": n_params, "arena_elems": a32.numel, "rounds": a.rounds}
+    for name, (arena, opt, bpe) in runs.items():
+        best = min(ms[name])
+        byt = bpe * arena.numel
+        rec[name] = {"ms": [round(x, 3) for x in ms[name]], "ms_min": round(best, 3), "algorithmic_bytes": byt,
+                     "gbs": round(byt / best / 1e6, 1), "frac_of_8TBs": round(byt / best / 1e-3 / HBM, 3)}
+    rec["state_bytes"] = {"adamw_fp32_moments": state32, "adamw_8bit": state8, "saved": state32 - state8,
+                          "adamw_8bit_per_param": round(state8 / n_params, 4)}
+    rec["speedup_8bit"] = round(rec["adamw_fp32"]["ms_min"] / rec["adamw_8bit"]["ms_min"], 3)
+    line = json.dumps(rec)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
