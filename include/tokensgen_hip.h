@@ -278,6 +278,14 @@ int tg_cfg_dpm_step_ex(const void* model_out, int branches, const void* x, const
 int tg_pca_inverse(const void* lat, const float* std16, const float* mean16, const float* comp, const float* pmean,
                    void* out, int frames, int ncoef, int hw, int cout, hipStream_t stream);
 
+/* T2To training input (train_cogvideo_t2to.py:1761-1773 `pca_normalization`: rearrange "b f c h w -> (b f h w) c", fp32, pca.transform
+ * (pca.py:56-58: a torch.matmul), `(y - mean) / std`, keep the first 16 coefficients, cast to the model dtype), per token row r:
+ *   y_j = sum_c (x[r][c] - pmean[c]) * comp[j][c]        out[r / hw][j][r % hw] = bf16( (y_j - mean16[j]) / std16[j] )      j < 16
+ * x bf16 [rows][D] (row stride ldx; rows ordered (b f h w)); comp fp32 [16][D] (components_[:16]); pmean fp32 [D] (mean_); mean16 / std16
+ * fp32 [16] (the normalisation's mean[:16] / std[:16]); out bf16 [rows / hw][16][hw] (= model_input [b f 16 h w]).  rows % hw == 0. */
+int tg_pca_project16(const void* x, long ldx, int rows, int D, const float* comp, const float* pmean, const float* mean16,
+                     const float* std16, int hw, void* out, hipStream_t stream);
+
 
 /* Training forward of one attention call: tg_attention_fwd with a single key segment that ALSO writes, per query row, the log-sum-exp of the
  * scaled scores in the log2 domain (lse fp32 [batch][heads][nq]): what flash-attention keeps for its backward
@@ -469,6 +477,18 @@ int tg_adamw8bit_step(void* param, float* grad, uint8_t* state1, uint8_t* state2
 int tg_vpred_loss_grad(const void* model_out, const void* noisy, const void* target, const float* coef, int frames, long frame_elems,
                        float inv_count, void* grad, float* partial, hipStream_t stream);
 long tg_vpred_loss_partial_floats(int frames, long frame_elems);
+
+/* Masked v-prediction loss of the T2To step (train_cogvideo_t2to.py:2125-2166; loss masks prepare_loss_masks :1098-1108).  Replaces
+ *   loss_b = sum(w_b * (|pred - target| * mask)^2) / sum(mask),  loss = mean_b loss_b,   mask = 1 on frames f < valid_frames[b]
+ * and its autograd gradient w.r.t. the model output.  Same element arithmetic as tg_vpred_loss_grad on the valid frames, with
+ *   inv_count_b = fp32( 1 / (valid_frames[b] * frame_elems * batch) )      (formed in double, one rounding)
+ * and zero gradient / zero partial contributions on the frames f >= valid_frames[b].  With valid_frames[b] == frames for every b the outputs
+ * are bitwise those of tg_vpred_loss_grad(..., inv_count = 1 / (frames * frame_elems * batch)).
+ * coef fp32 [batch * frames][3] = (sa, sb, w) per frame; valid_frames int32 [batch] (device); model_out / noisy / target / grad bf16
+ * [batch * frames][frame_elems]; partial fp32, tg_vpred_loss_partial_floats(batch * frames, frame_elems) floats (item b's loss = the sum of its
+ * frames' partials / (valid_frames[b] * frame_elems): a fixed order, deterministic, no atomics). */
+int tg_vpred_loss_grad_masked(const void* model_out, const void* noisy, const void* target, const float* coef, const int* valid_frames,
+                              int batch, int frames, long frame_elems, void* grad, float* partial, hipStream_t stream);
 
 /* Resampler's optional PCA low-rank filter (video_ipadapter/resampler.py:230-237: `pca.transform` -> zero every coefficient from 16 on ->
  * `pca.inverse_transform`, in the PCA's dtype = fp32, pca.py:56-66), per token:

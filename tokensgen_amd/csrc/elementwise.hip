@@ -217,6 +217,71 @@ __global__ __launch_bounds__(256) void vpred_loss_grad_kernel(const bf16_t* __re
     if (threadIdx.x == 0) partial[(long)f * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// Masked form of the loss above for the T2To step (train_cogvideo_t2to.py:2125-2166, masks from prepare_loss_masks :1098-1108): frame fl of item
+// b counts only while fl < valid[b]; the item's sum is normalised by its own mask sum valid[b] * E, not by frames * E.  The valid frames take
+// exactly the unmasked kernel's arithmetic (same rounding steps, same expression order), so with every frame valid the two kernels agree bit for
+// bit; the masked frames get a zero gradient and add 0 to their partials.  inv_count is formed in double and rounded once to fp32 (what the host
+// does for the unmasked kernel).
+__global__ __launch_bounds__(256) void vpred_loss_grad_masked_kernel(const bf16_t* __restrict__ out, const bf16_t* __restrict__ noisy,
+                                                                     const bf16_t* __restrict__ target, const float* __restrict__ coef,
+                                                                     const int* __restrict__ valid, int frames, long E, int batch,
+                                                                     bf16_t* __restrict__ grad, float* __restrict__ partial) {
+    __shared__ float red[4];
+    const int f = blockIdx.y;                         // global frame index b * frames + fl
+    const int b = f / frames, fl = f - b * frames;
+    const int vb = valid[b];
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    float term = 0.f;
+    if (e < E) {
+        const long i = (long)f * E + e;
+        if (fl < vb) {
+            const float sa = round_bf16(coef[3 * f]), sb = round_bf16(coef[3 * f + 1]), w = coef[3 * f + 2];
+            const float inv_count = (float)(1.0 / ((double)vb * (double)E * (double)batch));
+            const float pred = round_bf16(round_bf16(sa * bf16_to_f32(noisy[i])) - round_bf16(sb * bf16_to_f32(out[i])));
+            const float diff = round_bf16(pred - bf16_to_f32(target[i]));
+            term = w * round_bf16(diff * diff);
+            grad[i] = f32_to_bf16(-sb * (2.f * w * diff * inv_count));
+        } else {
+            grad[i] = f32_to_bf16(0.f);
+        }
+    }
+    term = wave_sum(term);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = term;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[(long)f * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// T2To training input (train_cogvideo_t2to.py:1761-1773 pca_normalization with pca.py:56-58 transform): per token row r = (b f h w), in fp32
+//   y_j = sum_c (x[r][c] - pmean[c]) * comp[j][c]        out[bf][j][s] = bf16( (y_j - mean16[j]) / std16[j] )      j < 16, s = r % hw
+// i.e. the first 16 normalised PCA coefficients written in the latents' [b f c h w] layout.  One workgroup per row, as pca_filter_kernel.
+__global__ __launch_bounds__(256) void pca_project16_kernel(const bf16_t* __restrict__ x, long ldx, int D, const float* __restrict__ comp,
+                                                            const float* __restrict__ pmean, const float* __restrict__ mean16,
+                                                            const float* __restrict__ std16, int hw, bf16_t* __restrict__ out) {
+    __shared__ float red[4][16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long r = blockIdx.x;
+    const bf16_t* xr = x + r * ldx;
+    float acc[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc[j] = 0.f;
+    for (int c = tid; c < D; c += 256) {
+        const float v = bf16_to_f32(xr[c]) - pmean[c];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) acc[j] = fmaf(v, comp[(long)j * D + c], acc[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const float t = wave_sum(acc[j]);
+        if (lane == 0) red[wave][j] = t;
+    }
+    __syncthreads();
+    if (tid < 16) {
+        const float y = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+        const long bf = r / hw, s = r - bf * hw;
+        out[(bf * 16 + tid) * hw + s] = f32_to_bf16((y - mean16[tid]) / std16[tid]);
+    }
+}
+
 }  // namespace
 
 extern "C" int tg_timestep_sinusoid(const int64_t* t, int n, int dim, void* emb, hipStream_t stream) {
@@ -324,6 +389,28 @@ extern "C" int tg_vpred_loss_grad(const void* model_out, const void* noisy, cons
     hipLaunchKernelGGL(vpred_loss_grad_kernel, dim3((unsigned)((frame_elems + 255) / 256), (unsigned)frames), dim3(256), 0, stream,
                        (const bf16_t*)model_out, (const bf16_t*)noisy, (const bf16_t*)target, coef, frame_elems, inv_count, (bf16_t*)grad, partial);
     TG_LAUNCH_CHECK("tg_vpred_loss_grad");
+    return TG_OK;
+}
+
+extern "C" int tg_vpred_loss_grad_masked(const void* model_out, const void* noisy, const void* target, const float* coef, const int* valid_frames,
+                                         int batch, int frames, long frame_elems, void* grad, float* partial, hipStream_t stream) {
+    TG_REQUIRE(model_out && noisy && target && coef && valid_frames && grad && partial, TG_ERR_ARG, "tg_vpred_loss_grad_masked: null pointer");
+    TG_REQUIRE(batch > 0 && frames > 0 && (long)batch * frames < 65536 && frame_elems > 0, TG_ERR_SHAPE,
+               "tg_vpred_loss_grad_masked: bad shape batch=%d frames=%d", batch, frames);
+    hipLaunchKernelGGL(vpred_loss_grad_masked_kernel, dim3((unsigned)((frame_elems + 255) / 256), (unsigned)(batch * frames)), dim3(256), 0, stream,
+                       (const bf16_t*)model_out, (const bf16_t*)noisy, (const bf16_t*)target, coef, valid_frames, frames, frame_elems, batch,
+                       (bf16_t*)grad, partial);
+    TG_LAUNCH_CHECK("tg_vpred_loss_grad_masked");
+    return TG_OK;
+}
+
+extern "C" int tg_pca_project16(const void* x, long ldx, int rows, int D, const float* comp, const float* pmean, const float* mean16,
+                                const float* std16, int hw, void* out, hipStream_t stream) {
+    TG_REQUIRE(x && comp && pmean && mean16 && std16 && out, TG_ERR_ARG, "tg_pca_project16: null pointer");
+    TG_REQUIRE(rows > 0 && D > 0 && ldx >= D && hw > 0 && rows % hw == 0, TG_ERR_SHAPE, "tg_pca_project16: bad shape rows=%d D=%d hw=%d", rows, D, hw);
+    hipLaunchKernelGGL(pca_project16_kernel, dim3((unsigned)rows), dim3(256), 0, stream, (const bf16_t*)x, ldx, D, comp, pmean, mean16, std16, hw,
+                       (bf16_t*)out);
+    TG_LAUNCH_CHECK("tg_pca_project16");
     return TG_OK;
 }
 

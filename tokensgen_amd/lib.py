@@ -56,6 +56,7 @@ PROTOTYPES = {
     "tg_adamw_step": [_vp, _vp, _vp, _vp, _l, _i, _f, _f, _f, _f, _f, _vp, _i, _vp],
     "tg_adamw8bit_step": [_vp] * 11 + [_i, _l, _i, _i, _f, _f, _f, _f, _f, _vp, _i, _vp],
     "tg_vpred_loss_grad": [_vp, _vp, _vp, _vp, _i, _l, _f, _vp, _vp, _vp],
+    "tg_vpred_loss_grad_masked": [_vp, _vp, _vp, _vp, _vp, _i, _i, _l, _vp, _vp, _vp],
     "tg_timestep_sinusoid": [_vp, _i, _i, _vp, _vp],
     "tg_rope_table_3d": [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp],
     "tg_patchify": [_vp, _vp, _l, _i, _i, _i, _i, _i, _vp],
@@ -65,6 +66,7 @@ PROTOTYPES = {
     "tg_cfg_dpm_step_ex": [_vp, _i, _vp, _vp, _vp, _vp, _f, _f, _vp, _i, _i, _i, _vp, _vp, _i, _l, _vp],
     "tg_pca_inverse": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "tg_pca_lowrank_filter": [_vp, _l, _vp, _vp, _vp, _l, _i, _i, _i, _vp],
+    "tg_pca_project16": [_vp, _l, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp],
     "tg_conv3d_cl": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _l, _i, _i, _i, _vp, _vp, _vp, _vp],
     "tg_conv3d_up2_subpixel": [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _l, _i, _vp, _vp, _vp],
     "tg_groupnorm_finalize": [_vp, _l, _i, _f, _vp, _vp],

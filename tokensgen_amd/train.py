@@ -16,6 +16,18 @@ from . import lib as L
 BF16 = torch.bfloat16
 
 
+def _vpred_coef(model_output, timesteps, alphas_cumprod):
+    """fp32 [B * F, 3] = (sqrt(acp_t), sqrt(1 - acp_t), 1 / (1 - acp_t)) per frame of model_output [B, F, ...]; timesteps [B, F] or [B]."""
+    B, F = model_output.shape[:2]
+    ts = timesteps.to(model_output.device).reshape(B, -1)
+    if ts.shape[1] == 1:
+        ts = ts.expand(B, F)
+    acp = alphas_cumprod.to(model_output.device, torch.float32)[ts.reshape(-1)]
+    # get_velocity casts the table to the sample dtype before the square roots (scheduling_dpm_cogvideox.py:524-532)
+    acp_b = acp.to(BF16)
+    return torch.stack([(acp_b ** 0.5).float(), ((1 - acp_b) ** 0.5).float(), 1.0 / (1.0 - acp)], dim=1).contiguous()
+
+
 @torch.no_grad()
 def vpred_loss_and_grad(model_output, noisy_model_input, model_input, timesteps, alphas_cumprod):
     """train_cogvideo_to2v.py:1990-2010.  model_output / noisy_model_input / model_input: bf16 [B, F, C, H, W]; timesteps int64 [B, F] (per-frame)
@@ -26,13 +38,7 @@ def vpred_loss_and_grad(model_output, noisy_model_input, model_input, timesteps,
         assert t.is_contiguous() and t.shape == model_output.shape
     B, F = model_output.shape[:2]
     E = model_output[0, 0].numel()
-    ts = timesteps.to(model_output.device).reshape(B, -1)
-    if ts.shape[1] == 1:
-        ts = ts.expand(B, F)
-    acp = alphas_cumprod.to(model_output.device, torch.float32)[ts.reshape(-1)]
-    # get_velocity casts the table to the sample dtype before the square roots (scheduling_dpm_cogvideox.py:524-532)
-    acp_b = acp.to(BF16)
-    coef = torch.stack([(acp_b ** 0.5).float(), ((1 - acp_b) ** 0.5).float(), 1.0 / (1.0 - acp)], dim=1).contiguous()
+    coef = _vpred_coef(model_output, timesteps, alphas_cumprod)
     grad = torch.empty_like(model_output)
     lib = L.load()
     partial = torch.empty(lib.tg_vpred_loss_partial_floats(B * F, E), dtype=torch.float32, device=model_output.device)
