@@ -419,6 +419,23 @@ typedef struct tg_colsum_item {
 } tg_colsum_item;
 int tg_colsum_multi(const tg_colsum_item* items, int count, int row_blocks, float* partial, hipStream_t stream);
 
+/* LoRA on the attention projections to_q / to_k / to_v / to_out.0 (peft LoraLayer on nn.Linear: y = x W^T + b + s (x A^T) B^T, s = lora_alpha / r;
+ * replaces get_peft_model / add_adapter of train_cogvideo_to2v.py:1326-1338 and the autograd of the adapter weights behind :1456-1481).
+ *   tg_lora_wgrad: G[n][j] = beta G[n][j] + scale sum_m Y[m][n] T[m][j]  (fp32 G, bf16 Y [batch][M][N] and T [batch][M][R], row and batch strides in
+ *                  elements; the token axis batch x M is the reduction axis).  N % 64 == 0, R % 64 == 0, R <= 384, any M.  G is addressed as
+ *                  G[n * g_stride_n + j * g_stride_j]: (R, 1) writes [N][R], (1, N) its transpose [R][N].  With T = x A^T: dB = s dy^T T (Y = dy);
+ *                  with dT = dy B: dA = s dT^T x (Y = x, T = dT, transposed output; to_q | to_k | to_v share x: R = 384, one launch).  beta = 0 never
+ *                  reads G; beta = 1 adds into a gradient arena.  Deterministic: the token axis is cut by the shape alone and the partials
+ *                  (ws: tg_lora_wgrad_ws_floats(batch * M, N, R) floats) are added in order.
+ *   tg_lora_merge: W_out[n][k] = bf16(W[n][k] + scale sum_j B[n][j] A[j][k])  (fuse_lora of the reference's load path, :1392-1416; B [N][R], A [R][K],
+ *                  W / W_out [N][K] with row strides; W_out == W allowed).  The sum is formed in fp64 (exact bf16 products; where W and the update cancel an
+ *                  fp32 sum would be many bf16 ulps off the small result) and rounded ONCE; a zero update returns W's bits. */
+long tg_lora_wgrad_ws_floats(int rows, int N, int R);
+int tg_lora_wgrad(const void* Y, long ldy, long y_batch_stride, const void* T, long ldt, long t_batch_stride, int M, int batch, int N, int R,
+                  float* G, long g_stride_n, long g_stride_j, float beta, float scale, float* ws, hipStream_t stream);
+int tg_lora_merge(const void* W, long ldw, const void* B, long ldb, const void* A, long lda, void* W_out, long ldo, int N, int K, int R, float scale,
+                  hipStream_t stream);
+
 /* Optimizer step on flat arenas (train_cogvideo_to2v.py:2012-2021: accelerator.clip_grad_norm_(transformer.parameters(), max_grad_norm), AdamW
  * (:1091-1098; betas / eps / weight decay of the yaml), zero_grad).  tg_adamw_step keeps fp32 moments (torch.optim.AdamW); the yaml's
  * use_8bit_adam (bitsandbytes AdamW8bit, block-wise 8-bit moments) is tg_adamw8bit_step below.

@@ -514,6 +514,45 @@ def attention_multi(main, rider, heads, scale, k_prescaled=False, retry=None, sp
     return main["out"], (rider["out"] if rider is not None else None)
 
 
+_LORA_WS = {}
+
+
+def lora_wgrad(y, t, out, scale=1.0, beta=0.0, transposed=False):
+    """out = beta * out + scale * y^T t, summed over the token axis (tg_lora_wgrad).  y [M, N] or [B, M, N], t likewise [.., R]: bf16, row / batch strides
+    allowed (column slices of wider buffers).  out fp32: [N, R], or [R, N] with transposed=True; any strides (a view of a gradient arena).  The partial-sum
+    workspace is kept per (rows, N, R, device): every use is ordered on the launch stream."""
+    _chk(y, "y"); _chk(t, "t")
+    B, M, N, ldy, sy = _bmk(y)
+    Bt, Mt, R, ldt, st = _bmk(t)
+    if (B, M) != (Bt, Mt):
+        raise ValueError(f"lora_wgrad: y{tuple(y.shape)} and t{tuple(t.shape)} differ in their token axes")
+    if not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != ((R, N) if transposed else (N, R)):
+        raise ValueError(f"lora_wgrad: out must be an fp32 GPU tensor of shape {(R, N) if transposed else (N, R)}, got {out.dtype} {tuple(out.shape)}")
+    gsn, gsj = (out.stride(1), out.stride(0)) if transposed else (out.stride(0), out.stride(1))
+    lib = L.load()
+    key = (B * M, N, R, str(y.device))
+    if key not in _LORA_WS:
+        _LORA_WS[key] = torch.empty(max(1, lib.tg_lora_wgrad_ws_floats(B * M, N, R)), dtype=torch.float32, device=y.device)
+    L.check(_launch(f"lora_wgrad_M{B * M}_N{N}_R{R}", lib.tg_lora_wgrad, _p(y), ldy, sy, _p(t), ldt, st, M, B, N, R, _p(out), gsn, gsj, float(beta), float(scale),
+                    _p(_LORA_WS[key]), _stream()), "tg_lora_wgrad")
+    return out
+
+
+def lora_merge(w, b, a, scale, out=None):
+    """out = bf16(w + scale * b @ a), summed in fp64 and rounded once (tg_lora_merge).  w [N, K], b [N, R], a [R, K] bf16 (row strides allowed);
+    out defaults to w (in place)."""
+    out = w if out is None else out
+    for n_, t_ in (("w", w), ("b", b), ("a", a), ("out", out)):
+        _chk(t_, n_)
+    N, K_ = w.shape
+    R = a.shape[0]
+    if b.shape != (N, R) or a.shape != (R, K_) or out.shape != w.shape:
+        raise ValueError(f"lora_merge: shape mismatch w{tuple(w.shape)} b{tuple(b.shape)} a{tuple(a.shape)} out{tuple(out.shape)}")
+    L.check(L.load().tg_lora_merge(_p(w), w.stride(0), _p(b), b.stride(0), _p(a), a.stride(0), _p(out), out.stride(0), N, K_, R, float(scale), _stream()),
+            "tg_lora_merge")
+    return out
+
+
 def timestep_sinusoid(t, dim, out):
     _chk(t, "t", torch.int64); _chk(out, "out")
     L.check(L.load().tg_timestep_sinusoid(_p(t), t.numel(), dim, _p(out), _stream()), "tg_timestep_sinusoid")

@@ -55,6 +55,8 @@ PROTOTYPES = {
     "tg_grad_clip_coef": [_vp, _l, _f, _vp, _vp, _vp],
     "tg_adamw_step": [_vp, _vp, _vp, _vp, _l, _i, _f, _f, _f, _f, _f, _vp, _i, _vp],
     "tg_adamw8bit_step": [_vp] * 11 + [_i, _l, _i, _i, _f, _f, _f, _f, _f, _vp, _i, _vp],
+    "tg_lora_wgrad": [_vp, _l, _l, _vp, _l, _l, _i, _i, _i, _i, _vp, _l, _l, _f, _f, _vp, _vp],
+    "tg_lora_merge": [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _f, _vp],
     "tg_vpred_loss_grad": [_vp, _vp, _vp, _vp, _i, _l, _f, _vp, _vp, _vp],
     "tg_vpred_loss_grad_masked": [_vp, _vp, _vp, _vp, _vp, _i, _i, _l, _vp, _vp, _vp],
     "tg_timestep_sinusoid": [_vp, _i, _i, _vp, _vp],
@@ -99,6 +101,7 @@ QUERIES = {
     "tg_colsum_partial_floats": [C.c_int, C.c_int],
     "tg_vpred_loss_partial_floats": [C.c_int, C.c_long],
     "tg_grad_norm_ws_floats": [],
+    "tg_lora_wgrad_ws_floats": [C.c_int, C.c_int, C.c_int],
 }
 
 TG_BWD_ONE_KERNEL = 1

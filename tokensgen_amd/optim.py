@@ -22,12 +22,16 @@ _ALIGN = 64          # elements: keeps every view 128-byte aligned (the GEMM wan
 def arena_order(names, num_layers):
     """Arena order = the order gradients become final in the backward (last block first, embeddings last, Resampler after the transformer), so
     that a bucket can be handed to RCCL as soon as the backward has passed its end.  Inside a block vip_to_{q,k,v} weights (and biases) are
-    adjacent: the fused [3D, D] projection weight is then a view of the arena, not a copy."""
+    adjacent: the fused [3D, D] projection weight is then a view of the arena, not a copy.  A block's LoRA tensors (`*.lora_{A,B}.weight`) sort with their block."""
     def block_key(n):
         for j, pat in enumerate(("vip_to_q.weight", "vip_to_k.weight", "vip_to_v.weight", "vip_to_q.bias", "vip_to_k.bias", "vip_to_v.bias")):
             if n.endswith(pat):
                 return (0, j, n)
-        return (1, 0, n)
+        # LoRA: the three lora_A of to_q | to_k | to_v side by side (one [3r, D] projection and ONE weight-gradient launch, train.To2VBlockTrainer), then the rest
+        for j, pat in enumerate(("to_q.lora_A.weight", "to_k.lora_A.weight", "to_v.lora_A.weight")):
+            if n.endswith(pat):
+                return (1, j, n)
+        return (2, 0, n)
     out = []
     for i in reversed(range(num_layers)):
         pre = f"transformer_blocks.{i}."

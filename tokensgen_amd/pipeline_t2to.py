@@ -102,7 +102,8 @@ class LongVGenCogVideoXPipeline:
         if timesteps is not None:
             raise NotImplementedError("custom timesteps: CogVideoXDPMScheduler.set_timesteps does not accept them")
         if attention_kwargs:
-            raise NotImplementedError("attention_kwargs (LoRA scale / masks) are not on the hot path")
+            raise NotImplementedError("attention_kwargs (LoRA scale / masks) are not on the hot path: a LoRA adapter is fused into the transformer's weights "
+                                      "before the call (transformer.fuse_lora(adapter, cfg, lora_scale=...)), a per-call `scale` is not supported")
         dev = self.device
         mean, std, pca = _load(longvgen_mean), _load(longvgen_std), _load(longvgen_pca)
         self._guidance_scale = guidance_scale

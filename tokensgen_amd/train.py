@@ -364,7 +364,7 @@ class To2VBlockTrainer:
     Weights come as a state dict with the reference's key names under `pre` (bf16 on the GPU).  Correct-first: separate launches, fp32 product
     tensors for the reductions; nothing in the inference path uses this class."""
 
-    def __init__(self, sd, pre, heads, n_text, n_vip, frames, vip_scale, eps=1e-5):
+    def __init__(self, sd, pre, heads, n_text, n_vip, frames, vip_scale, eps=1e-5, lora=None):
         # attention_processor.py:2126-2134: `scale` becomes a tensor of the activations' dtype before it multiplies (0.6 -> bf16 0.6015625), in the
         # forward and therefore in autograd's backward: round it once here, as the inference path does (transformer.py)
         vip_scale = float(torch.tensor(float(vip_scale), dtype=BF16))
@@ -377,6 +377,58 @@ class To2VBlockTrainer:
         self.bqkv = _cat_or_view([g(f"attn1.to_{n}.bias") for n in "qkv"])
         self.Wv = _cat_or_view([g(f"{P}vip_to_{n}.weight") for n in "qkv"])           # views of the parameter arena when q, k, v are adjacent there
         self.bv = _cat_or_view([g(f"{P}vip_to_{n}.bias") for n in "qkv"])
+        # LoRA (tokensgen_amd/lora.py): the adapter is applied UNMERGED, as peft computes it: y = x W^T + b + s (x A^T) B^T.  to_q | to_k | to_v read the same rows, so
+        # their three A matrices act as one [3r, D] projection (a view when the arena lays them out side by side, optim.arena_order)
+        self.lora, self.lora_qkv, self.lora_out = lora, False, False
+        self.grad_sink = None     # (ParamArena, scale): the adapter gradients are ADDED straight into the arena's fp32 gradient instead of being returned
+        if lora is not None:
+            la = lambda t, h: sd.get(f"{pre}.attn1.{t}.lora_{h}.weight")
+            have = [la(f"to_{n}", h) is not None for n in "qkv" for h in "AB"]
+            if any(have) and not all(have):
+                raise NotImplementedError(f"{pre}: LoRA on some of to_q / to_k / to_v only (they are adapted as a group here)")
+            self.lora_qkv, self.lora_out = all(have), la("to_out.0", "A") is not None
+            if (self.lora_qkv or self.lora_out) and lora.rank % 128:
+                raise NotImplementedError(f"LoRA rank {lora.rank}: the training path needs a multiple of 128 (the GEMM's N granule)")
+            if self.lora_qkv:
+                self.lA3 = _cat_or_view([la(f"to_{n}", "A") for n in "qkv"])
+                self.lB = [la(f"to_{n}", "B") for n in "qkv"]
+            if self.lora_out:
+                self.lAo, self.lBo = la("to_out.0", "A"), la("to_out.0", "B")
+
+    def lora_names(self):
+        """Names (relative to the block) of the adapter tensors this block applies."""
+        return ([f"attn1.to_{n}.lora_{h}.weight" for h in "AB" for n in "qkv"] if self.lora_qkv else []) + \
+               ([f"attn1.to_out.0.lora_{h}.weight" for h in "AB"] if self.lora_out else [])
+
+    def _scale_tab(self, tokens, width, batch, dev):
+        """Gate table whose every entry is s = lora_alpha / r (bf16: exact for the yamls' 0.5): `out += s * (a @ w^T)` through the GEMM's gated-residual epilogue."""
+        key = (tokens, width, batch)
+        if getattr(self, "_stab_key", None) != key:
+            self._stab_key = key
+            self._stab_t = (torch.full((1, 1, width), self.lora.scaling, dtype=BF16, device=dev), torch.zeros(max(tokens, 1024), dtype=torch.uint8, device=dev))
+        return K.GroupTable(self._stab_t[0].expand(batch, 1, -1), self._stab_t[1], [0], [0], [0], [0])
+
+    def _lora_wgrad(self, names, y, t, transposed, grads):
+        """Gradient of the adapter tensors `names` (one, or the three lora_A of to_q | to_k | to_v as ONE [3r, D] matrix) = s y^T t on tg_lora_wgrad: added into
+        the gradient arena when a sink is installed (beta = 1: no separate accumulate pass), else returned in `grads` as fp32."""
+        s = self.lora.scaling
+        r = t.shape[-1] // len(names)
+        if self.grad_sink is not None:
+            arena, gscale = self.grad_sink
+            outs = [arena.grad_view(f"{self.pre}.{n}") for n in names]
+            beta, scale = 1.0, s * gscale
+        else:
+            whole = torch.empty((t.shape[-1], y.shape[-1]) if transposed else (y.shape[-1], t.shape[-1]), dtype=torch.float32, device=y.device)
+            outs = [whole[j * r:(j + 1) * r] for j in range(len(names))] if len(names) > 1 else [whole]
+            beta, scale = 0.0, s
+            for n, o in zip(names, outs):
+                grads[n] = o
+        joint = _cat_or_view(outs) if len(outs) > 1 else outs[0]
+        if len(outs) == 1 or joint.data_ptr() == outs[0].data_ptr():        # side by side in memory: one launch (R = 3r) writes all of them
+            K.lora_wgrad(y, t, joint, scale=scale, beta=beta, transposed=transposed)
+        else:
+            for j, o in enumerate(outs):
+                K.lora_wgrad(y, t[..., j * r:(j + 1) * r], o, scale=scale, beta=beta, transposed=transposed)
 
     def _mod(self, emb, which):
         """[B, F, 9D] modulation tensor of norm{which}: columns 0..6D from norm.linear (per frame), 6D..9D from vip_norm.linear (frame 0 only)."""
@@ -424,6 +476,15 @@ class To2VBlockTrainer:
             K.gemm(Xn, self.Wv, self.bv, qkvv_pre, L.EPI_BIAS)
         # the backward needs the pre-norm Q / K (left in qkv_pre / qkvv_pre) AND the attention calls the post-norm rows: the norm + RoPE kernel writes the latter out of
         # place (a copy pass + the in-place pass before: two tensor passes less per projection); V is read where the projection left it
+        if self.lora_qkv:                                     # T = x A^T for the three projections at once, then y_j += s T_j B_j^T in place
+            r = self.lora.rank
+            T3 = e(B, N1, 3 * r)
+            K.gemm(Xn[:, :N1], self.lA3, None, T3, L.EPI_BIAS)
+            st = self._scale_tab(N, D, B, dev)
+            for j in range(3):
+                yj = qkv_pre[:, :, j * D:(j + 1) * D]
+                K.gemm(T3[:, :, j * r:(j + 1) * r], self.lB[j], None, yj, L.EPI_BIAS_GATE_RES, residual=yj, gate=st)
+            S["T3"] = T3
         qkv, qkvv = e(B, N1, 2 * D), e(B, N, 2 * D)
         A = f"{pre}.attn1."
         tab = lambda r: tuple(t.to(dev, torch.float32).contiguous() for t in r)
@@ -456,6 +517,14 @@ class To2VBlockTrainer:
         K.gemm(AO[:, N1:], sd[A + "to_out.0.weight"], sd[A + "to_out.0.bias"], y_attn, L.EPI_BIAS)
         X1 = e(B, N, D)
         K.gemm(AO, sd[A + "to_out.0.weight"], sd[A + "to_out.0.bias"], X1, L.EPI_BIAS_GATE_RES, residual=X0, gate=t1)
+        if self.lora_out:     # to_out.0's output gains s T B^T: un-gated on the kept vip rows, times the block's gate on the residual stream (gate table scaled by s)
+            r = self.lora.rank
+            To = e(B, N, r)
+            K.gemm(AO, self.lAo, None, To, L.EPI_BIAS)
+            K.gemm(To[:, N1:], self.lBo, None, y_attn, L.EPI_BIAS_GATE_RES, residual=y_attn, gate=self._scale_tab(N, D, B, dev))
+            t1s = K.GroupTable(mod1 * self.lora.scaling, self.tok_group, t1.rows, t1.shift_cols, t1.scale_cols, t1.gate_cols)
+            K.gemm(To, self.lBo, None, X1, L.EPI_BIAS_GATE_RES, residual=X1, gate=t1s)
+            S.update(To=To, AO=AO)
         mod2, t2 = self._mod(emb, 2)
         Xn2 = e(B, N, D)
         K.adaln_modulate(X1[:, :N1], Xn2[:, :N1], sd[f"{pre}.norm2.norm.weight"], sd[f"{pre}.norm2.norm.bias"], self.eps, t2)
@@ -536,6 +605,15 @@ class To2VBlockTrainer:
         # ---- attention residual (step 5), to_out ----
         dy_attn, tg1 = _gate_res_bwd(dX1, S["y_attn"], S["t1"], row0=N1)
         dAO = _dgrad(dy_attn.view(B * N, D), sd[A + "to_out.0.weight"], frozen=(self._wt, "out")).view(B, N, D)
+        train_lora = self.lora is not None and self.lora.is_trainable
+        if self.lora_out:     # dT = dy B (s is applied where it is exact: in the fp32 gradients' scale and in the gate of the accumulating GEMM), dAO += s dT A
+            r = self.lora.rank
+            dTo = torch.empty(B, N, r, dtype=BF16, device=dX2.device)
+            K.gemm(dy_attn, _weight_t(self.lBo, None), None, dTo, L.EPI_BIAS)
+            linear_backward_dx(dTo, self.lAo, accumulate_into=dAO, ones=self._scale_tab(N, D, B, dX2.device))
+            if train_lora:
+                self._lora_wgrad(["attn1.to_out.0.lora_B.weight"], dy_attn, S["To"], False, grads)
+                self._lora_wgrad(["attn1.to_out.0.lora_A.weight"], S["AO"], dTo, True, grads)
         # ---- the three attention calls, QK-norm + RoPE, projections ----
         # d(fused base / vip projection output), written third by third: the V thirds by the attention backward's own epilogues (bf16 of the fp32 dV: what a
         # conversion pass over the fp32 tensors wrote before — two passes per block less)
@@ -554,9 +632,21 @@ class To2VBlockTrainer:
         if dXn.is_contiguous() and D % 128 == 0:     # the base projection's share lands on the text + video rows through the GEMM's residual epilogue
             linear_backward_dx(d_pre_b, self.Wqkv, accumulate_into=dXn[:, :N1], ones=self._ones(N1, D, B, dX2.device), frozen=(self._wt, "qkv"))
         else:
+            if self.lora_qkv:
+                raise NotImplementedError("LoRA training needs the in-place accumulating dgrad (a contiguous stream of a width that is a multiple of 128)")
             dXn = dXn.float()
             dXn[:, :N1] += _dgrad(d_pre_b.reshape(B * N1, 3 * D), self.Wqkv, frozen=(self._wt, "qkv")).view(B, N1, D).float()
             dXn = dXn.to(BF16)
+        if self.lora_qkv:
+            r = self.lora.rank
+            dT3 = torch.empty(B, N1, 3 * r, dtype=BF16, device=dX2.device)
+            for j in range(3):
+                K.gemm(d_pre_b[:, :, j * D:(j + 1) * D], _weight_t(self.lB[j], None), None, dT3[:, :, j * r:(j + 1) * r], L.EPI_BIAS)
+            linear_backward_dx(dT3, self.lA3, accumulate_into=dXn[:, :N1], ones=self._scale_tab(N, D, B, dX2.device))
+            if train_lora:
+                for j, n in enumerate("qkv"):
+                    self._lora_wgrad([f"attn1.to_{n}.lora_B.weight"], d_pre_b[:, :, j * D:(j + 1) * D], S["T3"][:, :, j * r:(j + 1) * r], False, grads)
+                self._lora_wgrad([f"attn1.to_{n}.lora_A.weight" for n in "qkv"], S["Xn"][:, :N1], dT3, True, grads)
         # ---- norm1 ----
         dX0 = torch.empty(B, N, D, dtype=BF16, device=dX2.device)
         _adaln_bwd(S["X0"][:, :N1], dXn[:, :N1], dX0[:, :N1], sd[f"{pre}.norm1.norm.weight"], sd[f"{pre}.norm1.norm.bias"], self.eps, S["t1"], products=False,
@@ -582,10 +672,16 @@ class To2VTrainer:
     each block's two inputs; `backward` re-runs a block's forward with its intermediates kept, then its backward (the reference's
     torch.utils.checkpoint per block), so the live set is one block's activations + (layers x 2 residual streams)."""
 
-    def __init__(self, sd, num_attention_heads, num_layers, patch_size=2, vip_scale=1.0, eps=1e-5):
+    def __init__(self, sd, num_attention_heads, num_layers, patch_size=2, vip_scale=1.0, eps=1e-5, lora=None):
+        """lora: a lora.LoraConfig; the adapter tensors are the `*.lora_{A,B}.weight` entries of `sd` (lora.init_adapter / load_lora_weights).  They are applied
+        in every forward; they TRAIN (join `trainable`, get gradients) when lora.is_trainable, as the reference's yaml key decides (:1465-1467)."""
         self.sd, self.H, self.L, self.ps, self.s, self.eps = sd, num_attention_heads, num_layers, patch_size, float(vip_scale), eps
         self.D = sd["norm_final.weight"].shape[0]
-        self.trainable = sorted(k for k in sd if "vip_" in k)
+        self.lora = lora
+        self.grad_sink = None         # (ParamArena, scale), set by To2VTrainStep: the adapter gradients go straight into the arena (To2VBlockTrainer._lora_wgrad)
+        from .lora import is_lora_key
+        self.lora_keys = sorted(k for k in sd if is_lora_key(k) and lora.match(k.rsplit(".lora_", 1)[0])) if lora is not None else []
+        self.trainable = sorted([k for k in sd if "vip_" in k] + (self.lora_keys if lora is not None and lora.is_trainable else []))
         self._blocks = None
 
     activation_budget_bytes = None        # None: automatic (free device memory minus `activation_reserve_bytes`); 0: checkpoint every block
@@ -607,6 +703,14 @@ class To2VTrainer:
         import os
         os.makedirs(vip_ckpt_dir, exist_ok=True)
         torch.save({n: self.sd[n].detach().to("cpu").to(torch.float32) for n in self.trainable}, os.path.join(vip_ckpt_dir, "vip.pt"))
+
+    def save_lora_weights(self, lora_dir):
+        """`<dir>/pytorch_lora_weights.safetensors` in the diffusers layout the reference writes (train_cogvideo_to2v.py:1354): the adapter as the state dict
+        (the parameter arena) holds it now."""
+        from .lora import save_lora_weights
+        if not self.lora_keys:
+            raise RuntimeError("save_lora_weights: this trainer carries no LoRA adapter")
+        return save_lora_weights(lora_dir, {n: self.sd[n] for n in self.lora_keys})
 
     def reset_frozen_cache(self):
         """Forget the kept transposes of the FROZEN weights (To2VBlockTrainer._wt): call after frozen tensors of the state dict were overwritten IN PLACE (a trainer built
@@ -667,7 +771,7 @@ class To2VTrainer:
         B, Fr, C, Hh, Ww, Nt, Nv, Np, Fm = dims
         N1 = Nt + Nv
         if self._blocks is None or self._blocks[0].Nt != Nt or self._blocks[0].Np != Np or self._blocks[0].F != Fm:
-            self._blocks = [To2VBlockTrainer(sd, f"transformer_blocks.{i}", self.H, Nt, Np, Fm, self.s, self.eps) for i in range(self.L)]
+            self._blocks = [To2VBlockTrainer(sd, f"transformer_blocks.{i}", self.H, Nt, Np, Fm, self.s, self.eps, lora=self.lora) for i in range(self.L)]
         # the RoPE tables go to the device ONCE per forward (fp32, contiguous): every block's `.to(dev)` is then a no-op (six host-to-device copies per block before)
         rope, vrope, crope = (tuple(t_.to(X.device, torch.float32).contiguous() for t_ in r) for r in (rope, vrope, crope))
         self._ropes = (rope, vrope, crope)
@@ -737,6 +841,7 @@ class To2VTrainer:
             else:
                 blk.keep = True
                 blk.forward_x(self._ckpt[i], S["temb"], rope, vrope, crope)   # recompute with the intermediates kept
+            blk.grad_sink = self.grad_sink if (self.lora is not None and self.lora.is_trainable) else None
             g, dX = blk.backward_x(dX)
             blk.saved = None
             g = {f"transformer_blocks.{i}.{k}": v for k, v in g.items()}
@@ -857,11 +962,20 @@ class To2VTrainStep:
         last = self.micro % self.accum == 0
         scale = 1.0 / (self.accum * self.world)
 
+        direct = getattr(self.tr, "lora", None) is not None and self.tr.lora.is_trainable     # the adapter gradients are added into the arena by their own kernel
+        if direct:
+            self.tr.grad_sink = (self.arena, scale)
+
         def done(i, g):
             self.arena.accumulate(g, scale)
             if last and self.sync is not None:
-                self.sync.ready(max(self.arena.end_of(n) for n in g))
-        rest, d_vip = self.tr.backward(d_out, on_block_done=done)
+                names = list(g) + ([f"transformer_blocks.{i}.{n}" for n in self.tr._blocks[i].lora_names()] if direct else [])
+                self.sync.ready(max(self.arena.end_of(n) for n in names))
+        try:
+            rest, d_vip = self.tr.backward(d_out, on_block_done=done)
+        finally:
+            if direct:
+                self.tr.grad_sink = None
         self.arena.accumulate(rest, scale)
         if ctxs is not None:
             d_all = torch.zeros(alltok.shape, dtype=BF16, device=alltok.device)
