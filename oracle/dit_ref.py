@@ -173,7 +173,11 @@ def vip_attention(sd, pre, hidden, enc, heads, n_vip, scale, rope, vip_rope, con
     o1 = F.scaled_dot_product_attention(q, k, v)
     o2 = F.scaled_dot_product_attention(qx, kv, vv)
     o3 = F.scaled_dot_product_attention(qv, torch.cat([kx, kv], dim=2), torch.cat([vx, vv], dim=2))
-    s = torch.tensor(float(scale[0] if isinstance(scale, (list, tuple)) else scale), dtype=o2.dtype)
+    # attention_processor.py:2126-2134: `scale` becomes a tensor of the activations' dtype; a list with one entry per batch item weighs each item
+    # with its own entry (broadcast over heads, tokens, channels), a list of any other length stands for its first entry
+    s = torch.tensor([float(v) for v in scale] if isinstance(scale, (list, tuple)) else float(scale), dtype=o2.dtype, device=o2.device)
+    if s.ndim > 0:
+        s = s.view(-1, 1, 1, 1) if s.shape[0] == o2.shape[0] else s[0]
     if taps is not None:
         taps.update(q=q, k=k, v=v, qx=qx, kx=kx, vx=vx, qv=qv, kv=kv, vv=vv, o1=o1, o2=o2, o3=o3)
     o = torch.cat([o1 + s * o2, o3], dim=2)

@@ -104,6 +104,39 @@ def test_dit_medium_vs_oracle(nvid_hw, heads, layers):
     assert _rel(y, ref) < 8.5e-3           # measured 4.2e-3
 
 
+def test_dit_medium_per_batch_item_vip_scale_vs_oracle():
+    """The reference processor's `scale` list as long as the batch (attention_processor.py:2126-2134): the To2V model of the test above at
+    B = 2 with scale = [0.6, 0.3] — every batch item weighs its condensed-token attention with its own entry (transformer.py ->
+    tg_attn_problem.seg2_scale_batch) — against the oracle in bf16, at that test's tolerance."""
+    H, W = 6, 10
+    cfg = dict(num_attention_heads=4, attention_head_dim=64, num_layers=3, patch_size=2, time_embed_dim=128,
+               text_embed_dim=64, in_channels=16, out_channels=16)
+    vipcfg = dict(length=5 * 2 * 3, func_type="1", scale=[0.6, 0.3],
+                  resampler_params=dict(output_dim=128, num_height_queries=2, num_width_queries=3, num_temporal_queries=4))
+    sd = O.make_state_dict(cfg, n_vip_dim=128, seed=11)
+    m = _build(cfg, vipcfg, sd)
+    g = torch.Generator().manual_seed(12)
+    hs = torch.randn(2, 13, 16, H, W, generator=g)
+    enc = torch.randn(2, 21, 64, generator=g)
+    vip = torch.randn(2, 5, 128, 2, 3, generator=g)
+    ts = torch.randint(0, 1000, (2, 13), generator=g)
+    rope, vrope, crope = _tiny_ropes(H, W, 2.0)
+    sdb = {k: v.to(torch.bfloat16) for k, v in sd.items()}
+    args = (sdb, cfg, hs.bfloat16(), enc.bfloat16(), ts, vip.bfloat16(), rope, vrope, crope)
+    ref = O.dit_forward(*args, vip_scale=[0.6, 0.3])
+    y = m(hs.to(DEV, torch.bfloat16), enc.to(DEV, torch.bfloat16), ts.to(DEV), vip_encoder_hidden_states=vip.to(DEV, torch.bfloat16),
+          image_rotary_emb=rope, vip_image_rotary_emb=vrope, vip_condition_rotary_emb=crope, return_dict=False)[0]
+    assert _rel(y, ref) < 8.5e-3
+    for b in range(2):                                          # each item on its own: item 1 with item 0's weight would not hide in the batch norm
+        assert _rel(y[b], ref[b]) < 8.5e-3, b
+    # Entry 0 for both items moves item 1 of the oracle by 3.6e-3 only (a CPU figure), inside the tolerance above.  So, also: item 1 must sit closer to
+    # its own oracle than to that one — the bf16 noise of a right result is uncorrelated with the difference of the two oracles, so its distance to
+    # the wrong one is the larger (sqrt(noise^2 + 3.6e-3^2)); a batch-index mix-up reverses the order
+    wrong = O.dit_forward(*args, vip_scale=[0.6])
+    assert torch.equal(wrong[0], ref[0]) and float(_rel(wrong[1], ref[1])) > 2e-3
+    assert float(_rel(y[1], ref[1])) < float(_rel(y[1], wrong[1]))
+
+
 @pytest.mark.timeout(900)
 def test_dit_42_layers_depth_drift_vs_oracle(parity):
     """SURVEY §8c depth bound: the full 42-layer stack (2 heads x 64, D = 128, To2V processor, per-frame timesteps) through the HIP path

@@ -596,10 +596,13 @@ def test_attention_constant_shift_softmax(K, B, H, N1, NP, gain):
     vt3 = torch.zeros(B, H, 64, pad(N), dtype=BF, device=DEV); K.transpose_v(qkvv[:, :, 2 * D:], H, 0, N, vt3)
     retry = K.AttnRetry(N1, NP, H, B, DEV)
 
+    # the third shape (two-segment workgroups in the split tail) carries the reference's per-batch-item `scale` list (tg_attn_problem.seg2_scale_batch)
+    s_batch = [0.6015625, 0.3] if N1 == 2 * 512 + 150 else None
+
     def run(fast, split=None):
         a = torch.zeros(B, N, D, dtype=BF, device=DEV)
         K.attention_multi(dict(q1=qkv[:, :, :D], k1=qkv[:, :, D:2 * D], vt1=vt1, nk1=N1, out=a[:, :N1], q2=qkvv[:, :N1, :D], k2=qkvv[:, N1:, D:2 * D],
-                               vt2=vt2, nk2=NP, seg2_scale=0.6, kmax1=km1 if fast else None, kmax2=km2 if fast else None),
+                               vt2=vt2, nk2=NP, seg2_scale=0.6, kmax1=km1 if fast else None, kmax2=km2 if fast else None, seg2_scale_batch=s_batch),
                           dict(q1=qkvv[:, N1:, :D], k1=qkvv[:, :, D:2 * D], vt1=vt3, nk1=N, out=a[:, N1:], kmax1=km2 if fast else None), H, 0.125,
                           k_prescaled=True, retry=retry if fast else None, split=split)
         return a
@@ -620,8 +623,13 @@ def test_attention_constant_shift_softmax(K, B, H, N1, NP, gain):
     for h in sorted({0, H // 2, H - 1}):
         sl, ks, vs = slice(h * 64, h * 64 + 64), slice(D + h * 64, D + h * 64 + 64), slice(2 * D + h * 64, 2 * D + h * 64 + 64)
         sm = lambda q, k, v: torch.softmax(q.float() @ k.float().transpose(1, 2) * math.log(2.0), -1) @ v.float()
-        ref = sm(qkv[:, rows, sl], qkv[:, :, ks], qkv[:, :, vs]) + 0.6 * sm(qkvv[:, rows, sl], qkvv[:, N1:, ks], qkvv[:, N1:, vs])
+        w2 = torch.tensor(s_batch if s_batch is not None else [0.6] * B, dtype=torch.float32, device=DEV).view(B, 1, 1)
+        ref = sm(qkv[:, rows, sl], qkv[:, :, ks], qkv[:, :, vs]) + w2 * sm(qkvv[:, rows, sl], qkvv[:, N1:, ks], qkvv[:, N1:, vs])
         assert _rel(fast[:, rows, sl], ref) < 8e-3, h
+        if s_batch is not None:                                      # every batch item against its OWN weight, unsplit and (below) split
+            for b in range(B):
+                assert _rel(fast[b, rows, sl], ref[b]) < 8e-3, (h, b)
+                assert _rel(exact[b, rows, sl], ref[b]) < 8e-3, (h, b)
         refv = sm(qkvv[:, N1:, sl], qkvv[:, :, ks], qkvv[:, :, vs])
         assert _rel(fast[:, N1:, sl], refv) < 8e-3, h
     # key-axis split of the launch's half-round tail (tg_attn_workspace.split): at the launch-scale shape 768 + 96 = 864 = 3 x 256 + 96
@@ -634,7 +642,160 @@ def test_attention_constant_shift_softmax(K, B, H, N1, NP, gain):
             assert torch.equal(sp[:, N1:], base[:, N1:])                     # riders: whole workgroups
             assert not torch.equal(sp[:, :N1], base[:, :N1]) or (gain >= 5 and fastpath)   # main tail: two halves (gain 8, fast path: recomputed unsplit by the retry)
             assert _rel(sp, base) < 2e-3
+            if s_batch is not None:                                  # the split tail reads the weight of ITS batch item (attention.hip: the half-length workgroups)
+                for b in range(B):
+                    assert _rel(sp[b], base[b]) < 2e-3, b
         assert int(retry.buf[1:].abs().sum().item()) == 0
         assert retry.count() - n0 == (wgs if gain >= 5 else 0)
     else:
         assert retry.split is None or torch.equal(run(True, split=retry.split), fast)      # a launch that does not qualify ignores the workspace
+
+
+# ---- per-element attention checks against fp64 (tests/edge_bounds.py): "attention" in every name, so that the forced child of
+# ---- test_attention_cases_again_on_the_pingpong_kernel runs them through the 512-row kernel as well
+def _attn_qkv(B, H, nq, nk, seed, scale=1.0):
+    """q [B, nq, H*64], k / v [B, nk, H*64] as column slices of one fused buffer (row stride 3 H 64), and the V^T image."""
+    buf = _rand(B, max(nq, nk), 3 * H * 64, seed=seed, scale=scale)
+    return buf[:, :nq, :H * 64], buf[:, :nk, H * 64:2 * H * 64], buf[:, :nk, 2 * H * 64:]
+
+
+def _attn_vt(K, v, H):
+    B, nk = v.shape[0], v.shape[1]
+    vt = torch.full((B, H, 64, (nk + 63) // 64 * 64), 7.0, dtype=torch.bfloat16, device=DEV)
+    return K.transpose_v(v, H, 0, nk, vt)
+
+
+def _attn_out(B, nq, D):
+    """A strided output view inside a sentinel-filled buffer, and the check that the padding stayed untouched."""
+    full = torch.full((B, nq + 2, D + 16), 9.0, dtype=torch.bfloat16, device=DEV)
+    untouched = lambda: bool((full[:, 0] == 9.0).all() and (full[:, nq + 1] == 9.0).all() and (full[:, :, :8] == 9.0).all() and (full[:, :, 8 + D:] == 9.0).all())
+    return full[:, 1:1 + nq, 8:8 + D], untouched
+
+
+_KSCALE = 0.125 * 1.4426950408889634
+
+
+@pytest.mark.parametrize("prescaled", [False, True])
+@pytest.mark.parametrize("nq,nk1,nk2", [(1, 1, 0), (1, 65, 7), (63, 64, 1), (65, 63, 0), (129, 129, 65), (257, 7, 129), (511, 128, 63), (513, 1, 1)])
+def test_attention_edges_per_element(K, parity, nq, nk1, nk2, prescaled):
+    """nq < 64 and nq = 1, nk = 1, nk < 64 in segment 1, nk one past a 64-key tile, second segments of 1 / 7 / 63 / 65 / 129 keys: every output
+    element against fp64 within the derived bound."""
+    import edge_bounds as E
+    B, H = 2, 2
+    q1, k1, v1 = _attn_qkv(B, H, nq, nk1, seed=81)
+    if prescaled:
+        k1 = (k1.float() * _KSCALE).to(torch.bfloat16)
+    segs = [(q1, k1, v1, 1.0)]
+    out, untouched = _attn_out(B, nq, H * 64)
+    if nk2:
+        q2, k2, v2 = _attn_qkv(B, H, nq, nk2, seed=82)
+        if prescaled:
+            k2 = (k2.float() * _KSCALE).to(torch.bfloat16)
+        segs.append((q2, k2, v2, 0.6))
+        K.attention(q1, k1, _attn_vt(K, v1, H), nk1, out, H, 0.125, q2, k2, _attn_vt(K, v2, H), nk2, 0.6, k_prescaled=prescaled)
+    else:
+        K.attention(q1, k1, _attn_vt(K, v1, H), nk1, out, H, 0.125, k_prescaled=prescaled)
+    ref, bound = E.attention_ref(segs, H, 0.125, k_prescaled=prescaled)
+    parity(E.check(out, ref, bound)[0], 1.0, f"attention nq={nq} nk=({nk1},{nk2}) prescaled={prescaled}")
+    assert untouched()
+
+
+def test_attention_256_row_kernel_per_element(K, parity):
+    """B = 2, H = 48, nq = 2817: 1152 workgroups of 256 rows and 576 of 512 — the shape class between the 128-row and the 512-row kernels,
+    attn_fwd_kernel<2> in the default process.  Every head against fp64, one head at a time."""
+    import edge_bounds as E
+    B, H, nq, nk = 2, 48, 2817, 200
+    q, k, v = _attn_qkv(B, H, nq, nk, seed=83, scale=0.6)
+    out, untouched = _attn_out(B, nq, H * 64)
+    K.attention(q, k, _attn_vt(K, v, H), nk, out, H, 0.125)
+    qc, kc, vc, oc = q.cpu(), k.cpu(), v.cpu(), out.cpu()
+    worst = 0.0
+    for h in range(H):
+        sl = slice(h * 64, h * 64 + 64)
+        ref, bound = E.attention_ref([(qc[:, :, sl], kc[:, :, sl], vc[:, :, sl], 1.0)], 1, 0.125)
+        worst = max(worst, E.check(oc[:, :, sl], ref, bound)[0])
+    parity(worst, 1.0, "attention 256-row kernel B=2 H=48 nq=2817 nk=200")
+    assert untouched()
+
+
+@pytest.mark.parametrize("nq,nk", [(1, 65), (129, 129), (513, 1)])
+def test_attention_lse_edges_per_element(K, parity, nq, nk):
+    import edge_bounds as E
+    B, H = 2, 2
+    q, k, v = _attn_qkv(B, H, nq, nk, seed=84)
+    out, untouched = _attn_out(B, nq, H * 64)
+    _, lse = K.attention_lse(q, k, _attn_vt(K, v, H), nk, out, H, 0.125)
+    ref, bound = E.attention_ref([(q, k, v, 1.0)], H, 0.125)
+    parity(E.check(out, ref, bound)[0], 1.0, f"attention_lse out nq={nq} nk={nk}")
+    lref, lbound = E.attention_lse_ref(q, k, H, 0.125)
+    parity(E.check(lse, lref, lbound)[0], 1.0, f"attention_lse lse nq={nq} nk={nk}")
+    assert untouched()
+
+
+@pytest.mark.parametrize("nq", [1, 65, 513])
+def test_attention_single_key_returns_its_value_row_exactly(K, nq):
+    """nk = 1: the softmax weight is exactly 1 — every output row is the value row, bit for bit, in every kernel."""
+    B, H = 2, 2
+    q, k, v = _attn_qkv(B, H, nq, 1, seed=85)
+    out, untouched = _attn_out(B, nq, H * 64)
+    K.attention(q, k, _attn_vt(K, v, H), 1, out, H, 0.125)
+    assert torch.equal(out, v.expand(B, nq, H * 64)) and untouched()
+
+
+def test_attention_one_hot_keys_select_their_value_rows(K, parity):
+    """+-1 code keys k_j = c_j, queries q_i = 4 c_pi(i) for a seeded permutation pi, nk = 129 (one key past two 64-key tiles): the target score
+    is 4 * 64 / 8 = 32 nats and every other score at least 20 nats lower (asserted on the fp64 scores), so row i must be v_pi(i) within the
+    bound — a key-index error in the ragged tail, which random data averages away, selects a wrong row."""
+    import edge_bounds as E
+    B, H, n = 2, 2, 129
+    g = torch.Generator().manual_seed(86)
+    codes = torch.empty(0, 64)
+    while codes.shape[0] < n:                                        # seeded rejection: pairwise dot products <= 24
+        c = torch.randint(0, 2, (1, 64), generator=g).float() * 2 - 1
+        if codes.shape[0] == 0 or float((codes @ c.T).abs().max()) <= 24:
+            codes = torch.cat([codes, c])
+    perm = torch.stack([torch.stack([torch.randperm(n, generator=g) for _ in range(H)]) for _ in range(B)])       # [B, H, n]
+    kk = codes[None, :, None, :].expand(B, n, H, 64).reshape(B, n, H * 64)
+    qq = (4.0 * codes[perm]).permute(0, 2, 1, 3).reshape(B, n, H * 64)                                            # q[b, i, h] = 4 c_perm[b, h, i]
+    q, k = qq.to(torch.bfloat16).to(DEV), kk.to(torch.bfloat16).to(DEV)
+    v = _rand(B, n, H * 64, seed=87)
+    s = E._heads(q, H) @ E._heads(k, H).transpose(-1, -2) * 0.125                                                 # fp64 scores [B, H, n, n]
+    target = torch.gather(s, 3, perm[..., None])
+    off = s.scatter(3, perm[..., None], -1e9)
+    assert float(target.min()) == 32.0 and float(off.max()) <= 32.0 - 20.0
+    out, untouched = _attn_out(B, n, H * 64)
+    K.attention(q, k, _attn_vt(K, v, H), n, out, H, 0.125)
+    vh = E._heads(v, H)
+    want = torch.gather(vh, 2, perm[..., None].expand(B, H, n, 64)).transpose(1, 2).reshape(B, n, H * 64)         # v_pi(i), heads merged
+    _, bound = E.attention_ref([(q, k, v, 1.0)], H, 0.125)
+    leak = n * math.exp(-20.0) * float(vh.abs().max())                                                            # what the other keys can add at most
+    parity(E.check(out, want, bound + leak)[0], 1.0, "attention one-hot keys nk=129")
+    assert untouched()
+
+
+def test_attention_seg2_scale_per_batch_item(K, parity):
+    """tg_attn_problem.seg2_scale_batch (the reference processor's `scale` list as long as the batch, attention_processor.py:2126-2134):
+    B = 3 with three different weights, one of them negative, per element against fp64 — a batch-index mix-up gives an item another
+    item's weight."""
+    import edge_bounds as E
+    B, H, nq, nk1, nk2 = 3, 2, 200, 333, 100
+    wts = [0.6015625, 0.25, -1.5]
+    q1, k1, v1 = _attn_qkv(B, H, nq, nk1, seed=88)
+    q2, k2, v2 = _attn_qkv(B, H, nq, nk2, seed=89)
+    out, untouched = _attn_out(B, nq, H * 64)
+    K.attention_multi(dict(q1=q1, k1=k1, vt1=_attn_vt(K, v1, H), nk1=nk1, out=out, q2=q2, k2=k2, vt2=_attn_vt(K, v2, H), nk2=nk2, seg2_scale=0.6,
+                           seg2_scale_batch=wts), None, H, 0.125)
+    ref, bound = E.attention_ref([(q1, k1, v1, 1.0), (q2, k2, v2, wts)], H, 0.125)
+    parity(E.check(out, ref, bound)[0], 1.0, "attention seg2_scale_batch B=3")
+    assert untouched()
+
+
+def test_attention_seg2_scale_list_longer_than_16_raises(K):
+    B, H = 17, 1
+    q, k, v = _attn_qkv(B, H, 1, 1, seed=90)
+    out = torch.zeros(B, 1, 64, dtype=torch.bfloat16, device=DEV)
+    vt = _attn_vt(K, v, H)
+    with pytest.raises(RuntimeError, match=r"\(-2\)"):                    # TG_ERR_SHAPE
+        K.attention_multi(dict(q1=q, k1=k, vt1=vt, nk1=1, out=out, q2=q, k2=k, vt2=vt, nk2=1, seg2_scale=0.6, seg2_scale_batch=[0.5] * B), None, H, 0.125)
+    K.attention_multi(dict(q1=q, k1=k, vt1=vt, nk1=1, out=out, q2=q, k2=k, vt2=vt, nk2=1, seg2_scale=0.5), None, H, 0.125)   # the same launch without the list
+    assert torch.equal(out, (v.float() + (0.5 * v.float()).to(torch.bfloat16).float()).to(torch.bfloat16))     # nk = 1: O1 = O2 = v exactly
