@@ -317,7 +317,15 @@ int tg_attention_fwd_lse_ex(const void* q, long q_ld, long q_strideB, const void
  * P is recomputed from the log-sum-exp tile by tile.  Launches: statistics, then dK/dV per 256-key workgroup + dQ per 256-query workgroup (7 executed
  * GEMMs).  No atomics on the data: run-to-run deterministic.  lse: optional [batch][heads][nq] fp32 row log-sum-exp (log2 domain) written by
  * tg_attention_fwd_lse for the same q / k / scale — the statistics launch then only forms rowsum(dO o O); NULL: recomputed here.
- * (An independent correct-first implementation of the same mathematics lives in the TEST-ONLY library tests/libtg_crosscheck.so.) */
+ * (An independent correct-first implementation of the same mathematics lives in the TEST-ONLY library tests/libtg_crosscheck.so.)
+ * Roundings (what the per-element bounds of tests/train_bounds.py rest on); everything else is fp32:
+ *   - O is taken AS GIVEN (the bf16 tensor of the forward): D_i = sum_d dO_id O_id is an fp32 sum of its bits, not of a recomputed O.
+ *   - P = exp2(scale log2(e) q.k - lse) is formed in fp32 and rounded to bf16 ONCE, as the A operand of dV += P^T dO.
+ *   - dS = P (dP - D) is formed from the UNROUNDED fp32 P and rounded to bf16 ONCE, as the operand of dK += dS^T Q and dQ += dS K.
+ *   - in the dK/dV launch and the one-kernel form -lse / (scale log2(e)) and -D reach the S / dP accumulators through the matrix pipe, each as the sum of three bf16
+ *     pieces (truncation split, exact to 2^-24 of the value); the dQ launch subtracts the fp32 values themselves.
+ *   - dq / dk / dv are fp32 sums over the keys / queries (dq: times scale at the end; with a key split or the one-kernel form, partial sums added in a fixed order);
+ *     accumulate adds that result to the tensor in fp32; dv_bf16 is one bf16 rounding of the value dv receives. */
 int tg_attention_bwd(const void* q, long q_ld, long q_sb, const void* k, long k_ld, long k_sb, const void* v, long v_ld, long v_sb,
                      const void* o, long o_ld, long o_sb, const void* dout, long do_ld, long do_sb,
                      float* dq, long dq_ld, long dq_sb, float* dk, long dk_ld, long dk_sb, float* dv, long dv_ld, long dv_sb,
@@ -391,7 +399,11 @@ long tg_colsum_partial_floats(int rows, int cols);
  * per-element products whose column sums are the parameter gradients — t_dln = dy (1 + scale) [-> d beta], t_dlnx = t_dln x_hat [-> d gamma],
  * t_dyln = dy ln [-> d scale[g] over the rows of group g]; d shift[g] = column sums of dy.  t_*: fp32 [batch*tokens][dim], caller-allocated, or all
  * three NULL where the norm's parameters are frozen (text / video rows).  add (optional, bf16, laid out like dx): the gradient arriving over the
- * residual connection; dx = bf16(bf16(norm gradient) + add) — the sum autograd forms on bf16 tensors. */
+ * residual connection; dx = bf16(bf16(norm gradient) + add) — the sum autograd forms on bf16 tensors.
+ * Roundings (tests/train_bounds.py): the row statistics, x_hat, the two row means and dx = rstd (dln gamma - mean(dln gamma) - x_hat mean(dln gamma x_hat)), dln = dy (1 + scale),
+ * are fp32 and dx is rounded to bf16 once (twice with add, as written above); `ln` is rounded to bf16 BEFORE the product t_dyln = dy ln — the forward's ln, bit for bit up
+ * to the fp32 evaluation of x_hat gamma + beta — while t_dln and t_dlnx use the unrounded fp32 x_hat.  The 16-byte forms (dim % 8 == 0, 16-byte aligned rows; the row held
+ * in registers up to dim 4096, re-read beyond) and the scalar form compute the same expressions. */
 int tg_adaln_modulate_bwd(const void* x, long ldx, long strideX, const void* dy, long ld_dy, long stride_dy, void* dx, long ld_dx, long stride_dx,
                           const void* ln_weight, const void* ln_bias, float eps, int tokens, int dim, int batch, int modulate,
                           const tg_group_table* g, float* t_dln, float* t_dlnx, float* t_dyln, const void* add, long ld_add, long stride_add,

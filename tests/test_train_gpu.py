@@ -321,13 +321,16 @@ def test_attention_bwd_one_kernel_form_after_multi_stream_graph_work_in_a_child_
 
 
 def test_attention_bwd_two_kernel_form_in_a_child_process():
-    """TG_ATTN_BWD_FUSED=0: the dK/dV + dQ launches for the shapes the one-kernel form would take (same autograd comparison, same determinism check)."""
+    """TG_ATTN_BWD_FUSED=0: the dK/dV + dQ launches for the shapes the one-kernel form would take (same autograd comparison, same determinism check; and the one-kernel
+    shapes of test_train_edges_gpu.py per element against fp64).  A fresh child process: the form is chosen when the library is first used."""
     import os
     import subprocess
     import sys
     if os.environ.get("TG_ATTN_BWD_FUSED") == "0":
         pytest.skip("already inside a cross-check run")
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-m", "gpu", "-k", "test_attention_bwd_vs_autograd", "-x"],
+    edges = os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_train_edges_gpu.py")
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), edges, "-q", "-m", "gpu", "-k",
+                        "test_attention_bwd_vs_autograd or test_attention_bwd_edges_one_kernel_shapes", "-x"],
                        env=dict(os.environ, TG_ATTN_BWD_FUSED="0"), capture_output=True, text=True, timeout=600,
                        cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
