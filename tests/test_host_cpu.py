@@ -340,3 +340,66 @@ def test_stratified_timestep_sampling_per_rank():
         assert seen[0][0] == 0 and seen[-1][1] == 999            # 4096 draws per stratum of <= 1000 values: the ends are hit
     t = sample_timesteps(8192, 1000, 5, 8, explicit_uniform=False, generator=g)
     assert int(t.min()) == 0 and int(t.max()) == 999
+
+
+CONV_PLAN_TABLE = """
+    conv_in 8->128 8x240x360: in8 grid 1440 block 512 lds 56000 ksplit 1 reduce 0x0 case 0 splitk_floats 0
+    conv_out 128->3 8x240x360: halo_narrow grid 1440 block 512 lds 126208 ksplit 1 reduce 0x0 case 0 splitk_floats 0
+    conv_out 128->3 2x32x32: n16 grid 16 block 256 lds 65536 ksplit 1 reduce 0x0 case 0 splitk_floats 0
+    128->128 8x240x360: halo2 grid 1440 block 512 lds 131072 ksplit 1 reduce 0x0 case 0 splitk_floats 0
+    128->128 8x240x360 halo=0: w4_128 grid 1350 block 256 lds 163840 ksplit 1 reduce 0x0 case 0 splitk_floats 0
+    256->256 8x120x180: w4_256 grid 675 block 256 lds 131072 ksplit 1 reduce 0x0 case 0 splitk_floats 0
+    512->512 2x30x45: k128_splitk grid 440 block 256 lds 65536 ksplit 5 reduce 22x4 case 0 splitk_floats 6912000
+    128->128 2x32x32: k128_splitk grid 96 block 256 lds 65536 ksplit 6 reduce 16x1 case 0 splitk_floats 1572864
+    128->128 2x32x32 splitk=0: k128 grid 16 block 256 lds 65536 ksplit 1 reduce 0x0 case 0 splitk_floats 0
+    128->128 1x240x544 (255 patches): k128 grid 1020 block 256 lds 65536 ksplit 1 reduce 0x0 case 0 splitk_floats 0
+    128->128 1x256x512 (256 patches): halo2 grid 256 block 512 lds 131072 ksplit 1 reduce 0x0 case 0 splitk_floats 0
+    conv_out 128->3 1x240x544 (255 patches): n16 grid 1020 block 256 lds 65536 ksplit 1 reduce 0x0 case 0 splitk_floats 0
+    conv_out 128->3 1x256x512 (256 patches): halo_narrow grid 256 block 512 lds 126208 ksplit 1 reduce 0x0 case 0 splitk_floats 0
+    128->128 256x1x1 (256 patches, 2 rows): k128_splitk grid 12 block 256 lds 65536 ksplit 6 reduce 2x1 case 0 splitk_floats 196608
+    256->256 1x62x128 (31 tiles): k128_splitk grid 496 block 256 lds 65536 ksplit 4 reduce 62x2 case 4 splitk_floats 8126464
+    256->256 1x64x128 (32 tiles): w4_256 grid 32 block 256 lds 131072 ksplit 1 reduce 0x0 case 0 splitk_floats 8388608
+    128->2048 1x33x31 (M 1023): k128 grid 128 block 256 lds 65536 ksplit 1 reduce 0x0 case 0 splitk_floats 0
+    128->2048 1x32x32 (M 1024): w4_256 grid 32 block 256 lds 131072 ksplit 1 reduce 0x0 case 0 splitk_floats 0
+    128->128 1x23x89 (M 2047) w4=2: k128_splitk grid 96 block 256 lds 65536 ksplit 6 reduce 16x1 case 0 splitk_floats 1572096
+    128->128 1x32x64 (M 2048) w4=2: w4_128 grid 4 block 256 lds 163840 ksplit 1 reduce 0x0 case 0 splitk_floats 1572864
+    128->128 1x120x272 (255 tiles): k128_splitk grid 510 block 256 lds 65536 ksplit 2 reduce 255x1 case 2 splitk_floats 8355840
+    128->128 1x128x256 (256 tiles): k128 grid 256 block 256 lds 65536 ksplit 1 reduce 0x0 case 0 splitk_floats 0
+    128->128 2x32x32 halo=2: halo2 grid 4 block 512 lds 131072 ksplit 1 reduce 0x0 case 0 splitk_floats 1572864
+    256->256 2x32x32 halo=2: halo2 grid 8 block 512 lds 131072 ksplit 1 reduce 0x0 case 0 splitk_floats 4194304
+    conv_out 128->3 2x32x32 halo=2: halo_narrow grid 4 block 512 lds 126208 ksplit 1 reduce 0x0 case 0 splitk_floats 0
+    256->256 1x32x32: k128_splitk grid 128 block 256 lds 65536 ksplit 8 reduce 8x2 case 8 splitk_floats 2097152
+    256->256 1x32x32 w4=2: w4_256 grid 4 block 256 lds 131072 ksplit 1 reduce 0x0 case 0 splitk_floats 2097152
+    refused: T = 0: error -2: tg_conv3d_cl: bad spatial shape
+    refused: 8->64: error -2: tg_conv3d_cl: Cin = 8 is the 3x3x3, stride-1, 128-output-channel input convolution only
+    refused: 8->128 100x2048x2048: error -2: tg_conv3d_cl: too many tiles
+    refused: 8->128 2x1x1 with GroupNorm sums: error -2: tg_conv3d_cl: GroupNorm sums need at least as many 128-voxel rows (1) as 16 x 32 patches (2)
+    refused: Cin 100: error -2: tg_conv3d_cl: need Cin%64==0 and cout_pad%128==0 (or cout_pad in {16, 32, ..., 112}) (Cin=100 cout=128 cout_pad=128)
+    refused: kt 4: error -2: tg_conv3d_cl: unsupported kernel/stride/pad/up
+    refused: 128->3 with GroupNorm sums: error -2: tg_conv3d_cl: fused GroupNorm sums need cout in {128, 256, 512, ...} (cout=3)
+    refused: 128->7 (cout_pad 112) 4096x4096x4096: error -2: tg_conv3d_cl: too many tiles
+    refused: 128->1024 4096x4096x4096: error -2: tg_conv3d_cl: too many tiles
+    up2 256->256 8x120x180: up2_subpixel_shape_ok 1
+    up2 256->512 1x33x31 (M 1023): up2_subpixel_shape_ok 0
+    up2 256->512 1x32x32 (M 1024): up2_subpixel_shape_ok 1
+    up2 256->256 1x28x64 (4 x 7 tiles): up2_subpixel_shape_ok 0
+    up2 256->256 1x29x64 (4 x 8 tiles): up2_subpixel_shape_ok 1
+"""
+
+
+def test_conv_plan_table():
+    """tokensgen_amd/csrc/conv_plan.h: which kernel, grid, block, LDS bytes and split-K form tg_conv3d_cl launches for a shape, and what
+    tg_conv3d_splitk_floats / tg_conv3d_up2_subpixel_ok answer, as a pure host function printed by tests/conv_plan_table (tests/csrc/conv_plan_table.cpp:
+    the cases; 256 CUs).  The expectations are worked out by hand from the dispatcher's conditions: the layers of the real workload, then a case on each side of
+    every threshold — halo patches and 128 x 128 tiles against the CU count, 256-wide tiles against a eighth of it, M against 1024 and 2048, the knobs at 2
+    below launch scale — and one refused shape per message (code -2 and text).  `reduce AxB case K` is the split-K reduce launch; splitk_floats is the
+    128 x 128 kernel's workspace whether or not a halo or w4 kernel is taken first (callers cache it per shape)."""
+    import subprocess
+    exe = os.path.join(ROOT, "tests", "conv_plan_table")
+    assert os.path.exists(exe), "build first: python -c 'import __graft_entry__ as g; g.build()'"
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr[-2000:]
+    got, want = r.stdout.splitlines(), [ln.strip() for ln in CONV_PLAN_TABLE.strip().splitlines()]
+    assert len(got) == len(want)
+    for g, w in zip(got, want):
+        assert g == w

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 typedef uint16_t bf16_t;  // raw bfloat16 bits
 typedef __attribute__((ext_vector_type(8))) short bf16x8;
 typedef __attribute__((ext_vector_type(4))) short bf16x4;
@@ -10,11 +12,7 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
-#define TG_OK 0
-#define TG_ERR_ARG (-1)
-#define TG_ERR_SHAPE (-2)
-#define TG_ERR_ALIGN (-3)
-#define TG_ERR_HIP (-100)
+#include "tg_errors.h"
 
 // set the thread-local last-error string (api.cpp) and return `code`
 extern "C" int tg_set_error(int code, const char* fmt, ...);
@@ -76,6 +74,19 @@ __device__ __forceinline__ float wave_sum(float v) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
 }
+
+// compile-time loop: f(std::integral_constant<int, I>{}) for every I in [first I, N) — the index reaches the body as a constant (immediate offsets, template arguments)
+template <int I, int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+    if constexpr (I < N) {
+        f(std::integral_constant<int, I>{});
+        static_for<I + 1, N>(f);
+    }
+}
+
+// x * sigmoid(x) with exp2 + v_rcp_f32 instead of expf + division (the result is rounded to bf16 next): the GEMM's SiLU epilogue (gemm.hip) and the
+// VAE's streaming norm passes (vae.hip), which are VALU-bound before they are HBM-bound with a true division
+__device__ __forceinline__ float silu(float x) { return x * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x)); }
 
 // F.gelu(approximate="tanh"): 0.5 x (1 + tanh(u)), u = sqrt(2/pi) (x + 0.044715 x^3)  ==  x / (1 + exp(-2u)).
 // One v_exp + one v_rcp (1 ulp each; the result is rounded to bf16 right after) instead of a correctly rounded fp32 division:

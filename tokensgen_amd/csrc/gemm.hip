@@ -50,7 +50,7 @@ struct GemmParams {
     int group_m;                                  // m-tiles per n sweep of the 256^2 kernel's tile order (see launch())
 };
 
-// gelu_tanh(): common.h
+// gelu_tanh(), silu(): common.h
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 // two elements at a time: the polynomial part maps onto v_pk_mul_f32 / v_pk_fma_f32 (same operations, same results as gelu_tanh)
 __device__ __forceinline__ f32x2v gelu_tanh2(f32x2v x) {
@@ -59,7 +59,6 @@ __device__ __forceinline__ f32x2v gelu_tanh2(f32x2v x) {
     const f32x2v d = f32x2v{__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)} + 1.f;
     return x * f32x2v{__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
 }
-__device__ __forceinline__ float silu(float x) { return x * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x)); }
 
 template <int EPI>
 __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmParams p) {
@@ -492,14 +491,6 @@ constexpr int W4_LDS_BYTES = W4_GTAB_OFF + 4 * 64;
 
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
 
 template <int EPI>
 __global__ __launch_bounds__(256) void gemm256w4_kernel(GemmParams p) {

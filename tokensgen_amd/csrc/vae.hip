@@ -12,22 +12,12 @@
 
 #include <type_traits>
 #include "common.h"
+#include "conv_plan.h"
 #include "tokensgen_hip.h"
 
 namespace {
 
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
-constexpr int BM = 128, BN = 128, BK = 64;
-constexpr int GN_GROUPS = 32;
-constexpr int TILE_BYTES = BM * BK * 2;
-constexpr int STAGE_BYTES = 2 * TILE_BYTES;
+// BM, BN, BK, GN_GROUPS and every tile / LDS size a launch depends on (STAGE_BYTES, H2_*, CI_*, CW_*): conv_plan.h
 
 struct ConvParams {
     const bf16_t* x; int T, H, W, Cin;
@@ -319,14 +309,6 @@ __global__ __launch_bounds__(256) void conv3d_cl_kernel(ConvParams p) {
 // Voxel rows (64 B of channels) and weight rows sit at an 80-byte stride: 16 consecutive rows x one 16-byte slot = 64 distinct banks, and the
 // address stays linear in the voxel index, so a tap is still a uniform offset (the immediate offset field of the read).
 // ------------------------------------------------------------------------------------------------
-constexpr int H2_PH = 16, H2_PW = 32, H2_LW = H2_PW + 2, H2_ROWS = (H2_PH + 2) * H2_LW;      // 612 halo voxels
-constexpr int H2_STRIDE = 80;
-constexpr int H2_HALO_PIECES = (H2_ROWS * H2_STRIDE + 1023) / 1024;                            // 48
-constexpr int H2_HALO_BYTES = H2_HALO_PIECES * 1024;                                           // 49152
-constexpr int H2_W_BYTES = 128 * 64;                  // ring slot: 128 output channels x 32 k, 64-byte rows (16-byte slots XOR-swizzled by (row >> 2) & 3): 8 pieces, 2 per wave
-constexpr int H2_RING = 4;                            // weight stages in flight: the DMA of stage s+3 is issued at the top of stage s
-constexpr int H2_LDS = 2 * H2_HALO_BYTES + H2_RING * H2_W_BYTES;                               // 147456
-
 
 // NW waves per workgroup: 4 (one per SIMD, 128 voxels x 128 channels each) or 8 (two per SIMD, 64 voxels x 128 channels each: what one wave cannot
 // overlap with its own MFMAs — the blocked issue of its LDS-DMA pieces, its fragment-read waits — is covered by the other wave of the SIMD; twice the
@@ -767,10 +749,6 @@ __global__ __launch_bounds__(512) void conv3d_halo_narrow_kernel(ConvParams p) {
 // a per-lane table of 24 offsets, the 24 KB of weights sit in LDS, 96 MFMAs per wave.  The kernel is bound by its 256 B per voxel of output.
 // Epilogue (bias, bf16 store, GroupNorm sums per patch) as in conv3d_halo2_kernel.
 // ------------------------------------------------------------------------------------------------
-constexpr int CI_WROW = 208;                                   // LDS stride of a weight row: 96 k x 2 B + 16
-constexpr int CI_HALO = 3 * H2_ROWS * 16;                      // three frames x 612 voxels x 8 channels
-constexpr int CI_LDS = CI_HALO + 128 * CI_WROW;
-
 __global__ __launch_bounds__(512) void conv3d_in_kernel(ConvParams p) {
     constexpr int NW = 8, RW = H2_PH / NW, MI = 2 * RW;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -967,10 +945,6 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(const float* __
 // per-lane pointers (tap_src: padding -> zero page, frames before the window -> cache tensor) that are recomputed when the tap
 // changes, every Cin/64 stages.  Used for Cout % 256 == 0 without a temporal index map; everything else stays on conv3d_cl_kernel.
 // ------------------------------------------------------------------------------------------------
-constexpr int CW_OPER = 256 * 64 * 2;            // 32 KiB per operand per stage
-constexpr int CW_STAGE = 2 * CW_OPER;            // 64 KiB
-constexpr int CW_LDS = 2 * CW_STAGE;             // 128 KiB
-
 // NT = 256: 256 voxels x 256 channels, waves 2 x 2.  NT = 128 (Cout = 128): 512 voxels x 128 channels, waves 4 x 1 - the same 128x128 per
 // wave, every wave reads the whole W tile; 80 KiB per stage, i.e. all 160 KiB of LDS for the two stages.
 template <int NT>
@@ -1426,8 +1400,7 @@ __global__ __launch_bounds__(256) void gn_reduce_kernel(const float* __restrict_
 
 __device__ __forceinline__ float silu_f(float x) { return x / (1.f + __expf(-x)); }
 // the streaming norm passes are VALU-bound before they are HBM-bound (~30 VALU per element with a true division and per-value bf16 round
-// trips): pairwise rounding through one v_cvt_pk_bf16_f32, exp2 + v_rcp_f32 instead of expf + division (the result is rounded to bf16 next)
-__device__ __forceinline__ float silu_fast(float x) { return x * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x)); }
+// trips): pairwise rounding through one v_cvt_pk_bf16_f32, and silu() of common.h (exp2 + v_rcp_f32) instead of expf + division
 __device__ __forceinline__ void round_bf16_pair(float& a, float& b) {
     const uint32_t p = pack_bf16x2(a, b);
     a = bf16lo_to_f32(p);
@@ -1471,7 +1444,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const bf16_t* __restrict_
                 float a = fmaf(bf16lo_to_f32(u[i]), ga[2 * i], gb[2 * i]), b = fmaf(bf16hi_to_f32(u[i]), ga[2 * i + 1], gb[2 * i + 1]);
                 if (apply_silu) {
                     round_bf16_pair(a, b);
-                    a = silu_fast(a); b = silu_fast(b);
+                    a = silu(a); b = silu(b);
                 }
                 o[i] = pack_bf16x2(a, b);
             }
@@ -1605,7 +1578,7 @@ __global__ __launch_bounds__(256) void spatialnorm_row_kernel(const bf16_t* __re
             a += bf16lo_to_f32(zu[i]); b += bf16hi_to_f32(zu[i]);
             if (apply_silu) {
                 round_bf16_pair(a, b);                               // ... + conv_b(zq)
-                a = silu_fast(a); b = silu_fast(b);
+                a = silu(a); b = silu(b);
             }
             o[i] = pack_bf16x2(a, b);
         }
@@ -1693,158 +1666,64 @@ __global__ void tile_blend_kernel(const TT* __restrict__ a, TT* __restrict__ b, 
 
 inline unsigned grid_for(long total, int block = 256) { return (unsigned)min((total + block - 1) / block, (long)256 * 16); }
 
-// K ranges per tile for the 128 x 128 kernel: only when the plain launch would leave most CUs idle (fewer tiles than CUs) and the reduction
-// is long; aims at ~2 workgroups per CU (the kernel waits on every stage: a second resident workgroup hides that), >= 8 K steps per range.
-// TG_CONV_SPLITK=0 disables it (A/B runs, and the bitwise 4-wave-vs-128 test).  The w4 kernels are chosen first where they apply.
-static int conv_ksplit(long M, int cout, int cout_pad, long nk, int n_cu) {
-    if (!tg_knob(TG_KNOB_CONV_SPLITK) || cout != cout_pad || cout_pad % BN != 0 || cout > 512 || nk < 32) return 1;
-    const long tiles = ((M + BM - 1) / BM) * (cout_pad / BN);
-    if (tiles >= n_cu) return 1;
-    long ks = (2L * n_cu) / tiles;            // FLOOR: tiles * ks must not exceed the 2 n_cu resident slots — the first version rounded up, and the most common
-    if (ks > 8) ks = 8;                       // shape (88 tiles: 2 x 30 x 45 latent voxels x 512 channels) ran 528 workgroups = one full round + 16 stragglers
-    if (ks > nk / 8) ks = nk / 8;
-    return ks < 2 ? 1 : (int)ks;
-}
-
 }  // namespace
 
+// Which kernel, grid and LDS size: conv_plan() (conv_plan.h), a pure function of the shape, the three TG_CONV_* knobs and the CU count.  Here: what depends
+// on addresses, and the launch.
 extern "C" int tg_conv3d_cl(const void* x, int T, int H, int W, int Cin, const void* cache, const void* w, const void* bias,
                             int cout, int cout_pad, int kt, int kh, int kw, int stride, int pad, int up, const int32_t* t_map,
                             const void* residual, void* y, long ldy, int To, int Ho, int Wo, const void* zeros, float* gn_partial,
                             float* splitk_ws, hipStream_t stream) {
     TG_REQUIRE(x && w && y && zeros, TG_ERR_ARG, "tg_conv3d_cl: null pointer");
-    TG_REQUIRE(T > 0 && H > 0 && W > 0 && To > 0 && Ho > 0 && Wo > 0, TG_ERR_SHAPE, "tg_conv3d_cl: bad spatial shape");
-    if (Cin == 8) {                    // the encoder's conv_in: 8-channel input (3 used), weights packed [128][96] with k = tap * 3 + channel
-        TG_REQUIRE(cout == 128 && cout_pad == 128 && kt == 3 && kh == 3 && kw == 3 && stride == 1 && pad == 1 && up == 1 && !t_map && !residual && To == T &&
-                   Ho == H && Wo == W, TG_ERR_SHAPE, "tg_conv3d_cl: Cin = 8 is the 3x3x3, stride-1, 128-output-channel input convolution only");
-        TG_REQUIRE(tg_aligned16(x) && tg_aligned16(w) && (!cache || tg_aligned16(cache)) && (((uintptr_t)y) & 7) == 0 && ldy % 4 == 0, TG_ERR_ALIGN,
-                   "tg_conv3d_cl: alignment");
-        const long tiles_in = (long)To * ((Ho + H2_PH - 1) / H2_PH) * ((Wo + H2_PW - 1) / H2_PW), rows_in = ((long)To * Ho * Wo + BM - 1) / BM;
-        TG_REQUIRE(tiles_in < (1L << 31) && (long)(T + 2) * H * W * 8 < (1L << 31), TG_ERR_SHAPE, "tg_conv3d_cl: too many tiles");
-        TG_REQUIRE(!gn_partial || rows_in <= 4 * tiles_in, TG_ERR_SHAPE, "tg_conv3d_cl: GroupNorm sums need <= 4 rows of 128 voxels per 16 x 32 patch");
-        // every patch writes gn_partial[patch * 64 ..]: the buffer (tg_conv3d_gn_partial_floats) has one row per 128 voxels, so there may not be more patches than rows
-        TG_REQUIRE(!gn_partial || tiles_in <= rows_in, TG_ERR_SHAPE, "tg_conv3d_cl: GroupNorm sums need at least as many 128-voxel rows (%ld) as 16 x 32 patches (%ld)",
-                   rows_in, tiles_in);
-        ConvParams pi{(const bf16_t*)x, T, H, W, Cin, (const bf16_t*)cache, (const bf16_t*)w, (const bf16_t*)bias, cout, cout_pad, kt, kh, kw,
-                      stride, pad, up, nullptr, nullptr, (bf16_t*)y, ldy, To, Ho, Wo, (const bf16_t*)zeros, gn_partial, 1, nullptr};
-        hipLaunchKernelGGL(conv3d_in_kernel, dim3((unsigned)tiles_in), dim3(512), CI_LDS, stream, pi);
-        TG_LAUNCH_CHECK("tg_conv3d_cl(in)");
-        return TG_OK;
-    }
-    TG_REQUIRE(Cin % BK == 0 && (cout_pad % BN == 0 || (cout_pad < BN && cout_pad % 16 == 0)) && cout > 0 && cout <= cout_pad, TG_ERR_SHAPE,
-               "tg_conv3d_cl: need Cin%%64==0 and cout_pad%%128==0 (or cout_pad in {16, 32, ..., 112}) (Cin=%d cout=%d cout_pad=%d)", Cin, cout, cout_pad);
-    TG_REQUIRE(kt >= 1 && kt <= 3 && kh >= 1 && kh <= 3 && kw >= 1 && kw <= 3 && (stride == 1 || stride == 2) && (up == 1 || up == 2) &&
-               pad >= 0 && pad <= 1, TG_ERR_SHAPE, "tg_conv3d_cl: unsupported kernel/stride/pad/up");
-    TG_REQUIRE(tg_aligned16(x) && tg_aligned16(w) && tg_aligned16(zeros) && (!cache || tg_aligned16(cache)) && (((uintptr_t)y) & 1) == 0 &&
-               (cout % 4 != 0 || ((((uintptr_t)y) & 7) == 0 && ldy % 4 == 0)), TG_ERR_ALIGN, "tg_conv3d_cl: alignment");
-    ConvParams p{(const bf16_t*)x, T, H, W, Cin, (const bf16_t*)cache, (const bf16_t*)w, (const bf16_t*)bias, cout, cout_pad, kt, kh, kw,
-                 stride, pad, up, t_map, (const bf16_t*)residual, (bf16_t*)y, ldy, To, Ho, Wo, (const bf16_t*)zeros, gn_partial, 1, nullptr};
-    TG_REQUIRE(!gn_partial || (cout == cout_pad && cout % BN == 0 && (cout / GN_GROUPS) % 4 == 0), TG_ERR_SHAPE,
-               "tg_conv3d_cl: fused GroupNorm sums need cout in {128, 256, 512, ...} (cout=%d)", cout);
-    const long M = (long)To * Ho * Wo;
-    const int halo_on = (int)tg_knob(TG_KNOB_CONV_HALO);    // 0 never, 1 (default) at launch scale, 2 whenever legal (cross-check tests, tg_debug_set)
-    const int n_cu = tg_device_cus();
-    if (cout_pad % BN != 0 && halo_on && cout <= 4 && Cin == 128 && kt == 3 && kh == 3 && kw == 3 && pad == 1 && stride == 1 && up == 1 && !t_map && !residual &&
-        To == T && Ho == H && Wo == W && (long)(T + 2) * H * W * Cin < (1L << 31)) {
-        // the decoder's conv_out: halo-tiled, weights resident in LDS (17.7 -> 3 ms per decode against the 128 x 16 GEMM-shaped tile below)
-        const long h2tiles = (long)To * ((Ho + H2_PH - 1) / H2_PH) * ((Wo + H2_PW - 1) / H2_PW);
-        if ((halo_on == 2 || h2tiles >= n_cu) && h2tiles < (1L << 31)) {
-            const int lds = 2 * H2_HALO_BYTES + (cout + 1) * (27 * 128 * 2 + 64);
-            TG_DYN_LDS((conv3d_halo_narrow_kernel<128, 3>), 2 * H2_HALO_BYTES + 5 * (27 * 128 * 2 + 64));
-            hipLaunchKernelGGL((conv3d_halo_narrow_kernel<128, 3>), dim3((unsigned)h2tiles), dim3(512), lds, stream, p);
-            TG_LAUNCH_CHECK("tg_conv3d_cl(halo narrow)");
-            return TG_OK;
-        }
-    }
-    if (cout_pad % BN != 0) {          // narrow output (conv_out): 128 voxels x 16 channels per workgroup
-        const long tiles16 = ((M + BM - 1) / BM) * (cout_pad / 16);
-        TG_REQUIRE(tiles16 < (1L << 31), TG_ERR_SHAPE, "tg_conv3d_cl: too many tiles");
-        TG_DYN_LDS((conv3d_cl_kernel<1, 2, 1>), 2 * STAGE_BYTES);
-        hipLaunchKernelGGL((conv3d_cl_kernel<1, 2, 1>), dim3((unsigned)tiles16), dim3(256), 2 * STAGE_BYTES, stream, p);
-        TG_LAUNCH_CHECK("tg_conv3d_cl(n16)");
-        return TG_OK;
-    }
-    const long tiles = ((M + BM - 1) / BM) * (cout_pad / BN);
-    TG_REQUIRE(tiles < (1L << 31), TG_ERR_SHAPE, "tg_conv3d_cl: too many tiles");
-    // 4-wave kernel: 256x256 tiles.  Its launch threshold was "at least 2 tiles per CU" (set from single-stream timings in round 2: a launch of 270 tiles pays
-    // two rounds for 1.05); under the three tile streams a partial round is filled by the other tiles' launches, and what counts is the fill-path bytes per
-    // flop — half of the 128 x 128 kernel's.  Swept in round 4 (decode / encode wall, same box): 2 n_cu 0.469 / 0.246 s, n_cu 0.461 / 0.233, n_cu/2 0.446 / 0.228,
-    // n_cu/5 0.441 / 0.226, n_cu/8 0.436 / 0.220, n_cu/12 0.451 / 0.224 (there the 512-channel layers at 30 x 45 — 22 tiles — leave split-K).
-    // TG_CONV_W4=0: never, 2: whenever legal
-    const int w4 = (int)tg_knob(TG_KNOB_CONV_W4);
-    // Cout = 128, 3x3 spatial taps, stride 1, no upsampling: the halo-tiled kernel.  Against the GEMM-shaped kernels on the 8 x 240 x 360 layers:
-    // 128 -> 128: 0.70 vs 0.74 ms per launch; per clip 64 -> 128 (encoder conv_in) 13.3 vs 17.5 ms, 256 -> 128 45.6 vs 51.2 ms.  Why not more:
-    // see the stage loop's comment (the fill does not overlap with the issuing wave's MFMAs).
-    // TG_CONV_HALO: 0 never, 1 (default) at launch scale, 2 whenever legal (tests).
-    {
-        const long h2tiles = (long)To * ((Ho + H2_PH - 1) / H2_PH) * ((Wo + H2_PW - 1) / H2_PW);
-        const long rows128 = (M + BM - 1) / BM;
-        // Cout = 256 (two 128-channel slabs per patch) is legal but measured SLOWER than the 256 x 256 GEMM-shaped kernel (0.66 vs 0.55 ms on 256 -> 256 at
-        // 8 x 120 x 180: each slab re-stages the halo and the weights dominate the fill either way): taken only when forced (TG_CONV_HALO=2, tests)
-        if (halo_on && (cout == 128 || (cout == 256 && halo_on == 2)) && cout_pad == cout && kh == 3 && kw == 3 && pad == 1 && stride == 1 && up == 1 && !t_map && (kt == 1 || kt == 3) &&
-            To == T && Ho == H && Wo == W && (halo_on == 2 || h2tiles >= n_cu) && h2tiles <= rows128 &&
-            rows128 <= 4 * h2tiles && (long)(T + 2) * H * W * Cin < (1L << 31) && h2tiles < (1L << 31)) {
-            TG_DYN_LDS((conv3d_halo2_kernel<8>), H2_LDS);
-            // 8 waves (two per SIMD): 0.716 vs 0.730 ms (128 -> 128 at 8 x 240 x 360), 1.19 vs 1.26 ms (256 -> 128) against the one-wave-per-SIMD form of
-            // the same kernel, same box (profiles/NOTES.md, round 4)
-            hipLaunchKernelGGL(conv3d_halo2_kernel<8>, dim3((unsigned)(h2tiles * (cout / 128))), dim3(512), H2_LDS, stream, p);
-            TG_LAUNCH_CHECK("tg_conv3d_cl(halo)");
-            return TG_OK;
-        }
-    }
-    if (w4 && (w4 == 2 || ((M + 255) / 256) * (cout / 256) >= n_cu / 8) && cout == cout_pad && cout % 256 == 0 && !t_map && M >= 1024 && (long)kt * kh * kw * (Cin / 64) >= 4 && H * up < 2048 && W * up < 2048 &&
-        To < 512 && Ho < 2048 && Wo < 2048 && (long)kt * kh * kw * Cin < (1L << 21) && (long)(T + 2) * H * W * Cin < (1L << 31)) {
-        TG_DYN_LDS((conv3d_w4_kernel<256>), CW_LDS);
-        const long tiles4 = ((M + 255) / 256) * (cout / 256);
-        hipLaunchKernelGGL(conv3d_w4_kernel<256>, dim3((unsigned)tiles4), dim3(256), CW_LDS, stream, p);
-        TG_LAUNCH_CHECK("tg_conv3d_cl(w4)");
-        return TG_OK;
-    }
-    // Cout = 128: the 512x128 variant (plain 3x3x3 / 1x3x3 convolutions only: 16 A pieces per wave are too many for the general address path)
-    // (TG_CONV_W4 governs this variant too; measured: 128->128 layers 203 -> 187 ms per decode, 181 -> 162 ms per encode)
-    if (w4 && (w4 == 2 || (M + 511) / 512 >= 2L * n_cu) && cout == 128 && cout_pad == 128 && !t_map && stride == 1 && up == 1 && M >= 2048 &&
-        (long)kt * kh * kw * (Cin / 64) >= 4 && H < 2048 && W < 2048 && To < 512 && Ho < 2048 && Wo < 2048 && (long)kt * kh * kw * Cin < (1L << 21) &&
-        (long)(T + 2) * H * W * Cin < (1L << 31)) {
-        constexpr int LDS_N = 2 * (512 * 128 + 128 * 128);
-        TG_DYN_LDS((conv3d_w4_kernel<128>), LDS_N);
-        const long tiles5 = (M + 511) / 512;
-        hipLaunchKernelGGL(conv3d_w4_kernel<128>, dim3((unsigned)tiles5), dim3(256), LDS_N, stream, p);
-        TG_LAUNCH_CHECK("tg_conv3d_cl(w4n)");
-        return TG_OK;
-    }
-    TG_DYN_LDS((conv3d_cl_kernel<2, 4, 4>), 2 * STAGE_BYTES);
-    // split-K: the small-M layers (the 512-channel layers at 30 x 45 latent: 88 tiles for 256 CUs, each walking 216 K steps alone on its CU)
-    p.ksplit = conv_ksplit(M, cout, cout_pad, (long)kt * kh * kw * (Cin / BK), n_cu);
-    if (p.ksplit > 1) {
-        TG_REQUIRE(splitk_ws, TG_ERR_ARG, "tg_conv3d_cl: this shape runs split-K (tg_conv3d_splitk_floats > 0) and needs the workspace");
-        p.kpart = splitk_ws;
-        hipLaunchKernelGGL((conv3d_cl_kernel<2, 4, 4>), dim3((unsigned)(tiles * p.ksplit)), dim3(256), 2 * STAGE_BYTES, stream, p);
-        const dim3 rgrid((unsigned)((M + BM - 1) / BM), (unsigned)(cout / 128));
-#define TG_SPLITK_REDUCE(KS)                                                                                                                \
-    hipLaunchKernelGGL(conv_splitk_reduce_kernel<KS>, rgrid, dim3(256), 0, stream, (const float*)splitk_ws, p.ksplit, M, cout, (const bf16_t*)bias, \
-                       (const bf16_t*)residual, (bf16_t*)y, ldy, gn_partial)
-        switch (p.ksplit) {
-            case 2: TG_SPLITK_REDUCE(2); break;
-            case 4: TG_SPLITK_REDUCE(4); break;
-            case 8: TG_SPLITK_REDUCE(8); break;
-            default: TG_SPLITK_REDUCE(0); break;
-        }
+    const ConvPlan pl = conv_plan(ConvShape{T, H, W, Cin, cout, cout_pad, kt, kh, kw, stride, pad, up, To, Ho, Wo, t_map != nullptr, residual != nullptr, gn_partial != nullptr},
+                                  ConvKnobs{(int)tg_knob(TG_KNOB_CONV_HALO), (int)tg_knob(TG_KNOB_CONV_W4), tg_knob(TG_KNOB_CONV_SPLITK) != 0}, tg_device_cus());
+    TG_REQUIRE(pl.err == TG_OK, pl.err, "%s", pl.msg);      // every shape error comes before the alignment error (a call with both faults gets the shape one)
+    const bool y_x4 = (((uintptr_t)y) & 7) == 0 && ldy % 4 == 0;      // 8-byte stores of four output channels
+    TG_REQUIRE(tg_aligned16(x) && tg_aligned16(w) && (!cache || tg_aligned16(cache)) &&
+               (Cin == 8 ? y_x4 : tg_aligned16(zeros) && (((uintptr_t)y) & 1) == 0 && (cout % 4 != 0 || y_x4)), TG_ERR_ALIGN, "tg_conv3d_cl: alignment");
+    TG_REQUIRE(pl.ksplit == 1 || splitk_ws, TG_ERR_ARG, "tg_conv3d_cl: this shape runs split-K (tg_conv3d_splitk_floats > 0) and needs the workspace");
+    const ConvParams p{(const bf16_t*)x, T, H, W, Cin, (const bf16_t*)cache, (const bf16_t*)w, (const bf16_t*)bias, cout, cout_pad, kt, kh, kw,
+                       stride, pad, up, t_map, (const bf16_t*)residual, (bf16_t*)y, ldy, To, Ho, Wo, (const bf16_t*)zeros, gn_partial, pl.ksplit,
+                       pl.ksplit > 1 ? splitk_ws : nullptr};
+    // max_lds: the most dynamic LDS any launch of this kernel asks for (set once per device)
+#define TG_CONV_LAUNCH(kernel, max_lds)                                                              \
+    do {                                                                                             \
+        TG_DYN_LDS(kernel, max_lds);                                                                 \
+        hipLaunchKernelGGL(kernel, dim3(pl.grid), dim3(pl.block), pl.lds, stream, p);                \
+    } while (0)
+    const char* what = "tg_conv3d_cl";
+    switch (pl.kernel) {
+        case CONV_IN8: hipLaunchKernelGGL(conv3d_in_kernel, dim3(pl.grid), dim3(pl.block), pl.lds, stream, p); what = "tg_conv3d_cl(in)"; break;
+        case CONV_HALO_NARROW: TG_CONV_LAUNCH((conv3d_halo_narrow_kernel<128, 3>), 2 * H2_HALO_BYTES + 5 * HN_WROW); what = "tg_conv3d_cl(halo narrow)"; break;
+        case CONV_N16: TG_CONV_LAUNCH((conv3d_cl_kernel<1, 2, 1>), 2 * STAGE_BYTES); what = "tg_conv3d_cl(n16)"; break;
+        case CONV_HALO2: TG_CONV_LAUNCH((conv3d_halo2_kernel<8>), H2_LDS); what = "tg_conv3d_cl(halo)"; break;
+        case CONV_W4_256: TG_CONV_LAUNCH((conv3d_w4_kernel<256>), CW_LDS); what = "tg_conv3d_cl(w4)"; break;
+        case CONV_W4_128: TG_CONV_LAUNCH((conv3d_w4_kernel<128>), CW_LDS_N128); what = "tg_conv3d_cl(w4n)"; break;
+        case CONV_128:
+        case CONV_128_SPLITK:
+            TG_CONV_LAUNCH((conv3d_cl_kernel<2, 4, 4>), 2 * STAGE_BYTES);
+            if (pl.kernel == CONV_128) break;
+            what = "tg_conv3d_cl(split-K)";
+#define TG_SPLITK_REDUCE(KS)                                                                                                                             \
+    hipLaunchKernelGGL(conv_splitk_reduce_kernel<KS>, dim3(pl.rgrid_x, pl.rgrid_y), dim3(256), 0, stream, (const float*)splitk_ws, pl.ksplit, (long)To * Ho * Wo, \
+                       cout, (const bf16_t*)bias, (const bf16_t*)residual, (bf16_t*)y, ldy, gn_partial)
+            switch (pl.reduce_ks) {
+                case 2: TG_SPLITK_REDUCE(2); break;
+                case 4: TG_SPLITK_REDUCE(4); break;
+                case 8: TG_SPLITK_REDUCE(8); break;
+                default: TG_SPLITK_REDUCE(0); break;
+            }
 #undef TG_SPLITK_REDUCE
-        TG_LAUNCH_CHECK("tg_conv3d_cl(split-K)");
-        return TG_OK;
+            break;
     }
-    hipLaunchKernelGGL((conv3d_cl_kernel<2, 4, 4>), dim3((unsigned)tiles), dim3(256), 2 * STAGE_BYTES, stream, p);
-    TG_LAUNCH_CHECK("tg_conv3d_cl");
+#undef TG_CONV_LAUNCH
+    TG_LAUNCH_CHECK(what);
     return TG_OK;
 }
 
+// tg_device_cus(), as in the launcher: it answers 256 CUs where there is no device, so the query also works on a host without a GPU
 extern "C" long tg_conv3d_splitk_floats(int Cin, int cout, int cout_pad, int kt, int kh, int kw, int To, int Ho, int Wo) {
-    int n_cu = 0, dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
-    const long M = (long)To * Ho * Wo;
-    const int ks = conv_ksplit(M, cout, cout_pad, (long)kt * kh * kw * (Cin / BK), n_cu);
-    return ks > 1 ? (long)ks * M * cout_pad : 0;
+    return conv_splitk_floats(Cin, cout, cout_pad, kt, kh, kw, To, Ho, Wo, tg_knob(TG_KNOB_CONV_SPLITK) != 0, tg_device_cus());
 }
 
 extern "C" long tg_groupnorm_partial_floats(long V, int C) {
@@ -1863,13 +1742,7 @@ extern "C" int tg_groupnorm_stats(const void* x, long V, int C, float eps, float
     return TG_OK;
 }
 
-// ---- nearest x2 upsampling + 3x3 convolution as four 2x2 phase convolutions on the LOW-resolution input (see the header) ----
-static bool up2_subpixel_shape_ok(int T, int H, int W, int Cin, int cout, int n_cu) {
-    const long M = (long)T * H * W;
-    return Cin % 64 == 0 && cout % 256 == 0 && M >= 1024 && 4 * ((M + 255) / 256) * (cout / 256) >= n_cu / 8 && 4L * (Cin / 64) >= 4 && H < 1024 && W < 1024 && T < 512 &&
-           4L * Cin < (1L << 21) && (long)(T + 2) * H * W * Cin < (1L << 31) && 4L * M * cout < (1L << 40);
-}
-
+// ---- nearest x2 upsampling + 3x3 convolution as four 2x2 phase convolutions on the LOW-resolution input (see the header; up2_subpixel_shape_ok: conv_plan.h) ----
 extern "C" long tg_conv3d_up2_subpixel_ok(int T, int H, int W, int Cin, int cout) {
     return up2_subpixel_shape_ok(T, H, W, Cin, cout, tg_device_cus()) && tg_knob(TG_KNOB_CONV_W4) != 0 ? 1 : 0;
 }
