@@ -91,6 +91,18 @@ int tg_gemm_bf16_qkv(const void* A1, long strideA1, const void* W1, const void* 
                      const void* A2, long strideA2, const void* W2, const void* bias2, void* C2, long strideC2, int M2, void* Vt2, long vt_ld2,
                      long lda, long ldw, long ldc, int N, int K, int batch, int v_col0, hipStream_t stream);
 
+/* A linear layer with an UNMERGED LoRA adapter in one launch: C[b,m,:] = bf16(A[b,m,:] @ W^T + bias + scale * (T[b,m,:] @ B^T)), W [N,K], T [batch][M][R]
+ * (the adapter's down-projection x lora_A^T, bf16, row stride ldt, batch stride strideT), B = lora_B [N][R] (row stride ldb), scale = lora_alpha / r as an
+ * fp32 argument — peft's LoraLayer on nn.Linear as train_cogvideo_t2to.py:1416-1427 adds it to the attention projections (yaml keys use_lora, lora_params).
+ * The R / 64 tail k-steps run first into the tile's fp32 accumulators, which are multiplied by `scale` once (exact in fp32, no bf16 rounding of the scale;
+ * scale == 0 clears them: the result is then bitwise tg_gemm_bf16's with TG_EPI_BIAS), and the main K loop runs on top: no second pass over C.  The same
+ * call is the frozen-base input gradient dX = dY W + scale * dT A (W := W^T, T := dT, B := A^T).
+ * 4-wave kernel shapes only: M >= 1024, N % 256 == 0, K % 64 == 0, K >= 256, R % 64 == 0, 64 <= R <= 384, leading dimensions < 2^21 — TG_ERR_SHAPE
+ * otherwise, and the caller runs tg_gemm_bf16 twice (TG_EPI_BIAS, then TG_EPI_BIAS_GATE_RES with a gate table holding `scale`). */
+int tg_gemm_bf16_lora(const void* A, long lda, long strideA, const void* W, long ldw, const void* bias,
+                      const void* T, long ldt, long strideT, const void* B, long ldb, float scale,
+                      void* C, long ldc, long strideC, int M, int N, int K, int R, int batch, hipStream_t stream);
+
 /* y = LayerNorm(x; w, b, eps) * (1 + scale[g]) + shift[g], g = group of the token.  One pass, fp32 stats.
  * modulate == 0: plain affine LayerNorm (norm_final, cogvideox_transformer_3d.py:741).
  * Replaces normalization.py:441-460 (CogVideoXLayerNormZero), :477-488 (VIP), :70-92 (AdaLayerNorm).

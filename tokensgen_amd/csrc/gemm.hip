@@ -50,6 +50,14 @@ struct GemmParams {
     int group_m;                                  // m-tiles per n sweep of the 256^2 kernel's tile order (see launch())
 };
 
+// low-rank tail of tg_gemm_bf16_lora (4-wave kernel only): C = bf16(A W^T + bias + s (T B^T)), T [batch][M][R], B [N][R].  The tail is R / 64
+// more k-stages in FRONT of the main K loop, fetched through the same stage stream from a second pair of operands
+struct LoraTail {
+    const bf16_t* T; long ldt; long sTb;
+    const bf16_t* B; long ldb;
+    int R; float s;
+};
+
 // gelu_tanh(), silu(): common.h
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 // two elements at a time: the polynomial part maps onto v_pk_mul_f32 / v_pk_fma_f32 (same operations, same results as gelu_tanh)
@@ -492,8 +500,19 @@ constexpr int W4_LDS_BYTES = W4_GTAB_OFF + 4 * 64;
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-template <int EPI>
-__global__ __launch_bounds__(256) void gemm256w4_kernel(GemmParams p) {
+// LORA (tg_gemm_bf16_lora, bias epilogue, one problem, no V^T): every output tile runs ntl = R / 64 stages on (T, B) first, multiplies its accumulators
+// by s once, then runs the main K loop on top — no second accumulator set, and s is applied in fp32.  The DMA cursor switches its operand pair (buffer
+// resources, per-lane offsets, piece strides) where it crosses from the tail into the main loop and back at the next tile; every stage is still 16 pieces
+// into the same buffers, so the counted vmcnt waits, the barriers and the fragment reads are the main loop's, untouched.
+//
+// The tail arrives as an optional second kernel argument (`Tail...` is empty or one LoraTail): the plain instantiations keep their one-argument signature.
+__device__ __forceinline__ LoraTail tail_of() { return LoraTail{}; }
+__device__ __forceinline__ LoraTail tail_of(const LoraTail& t) { return t; }
+
+template <int EPI, typename... Tail>
+__global__ __launch_bounds__(256) void gemm256w4_kernel(GemmParams p, Tail... tail) {
+    constexpr bool LORA = sizeof...(Tail) != 0;
+    const LoraTail lt = tail_of(tail...);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -505,6 +524,7 @@ __global__ __launch_bounds__(256) void gemm256w4_kernel(GemmParams p) {
     const int nwg1 = tiles_m1 * tiles_n * p.batch;
     const int nwg = nwg1 + tiles_m2 * tiles_n * p.batch;
     const int nst = p.K / BK3;
+    const int ntl = LORA ? lt.R / BK3 : 0;         // tail stages in front of every tile's main K loop
 
     struct Coord { int sec, b, m0, n0; };
     auto coords = [&](int id) {
@@ -536,13 +556,35 @@ __global__ __launch_bounds__(256) void gemm256w4_kernel(GemmParams p) {
         voffA[odd] = (int)(((long)(wave * 64 + row) * p.lda + dslot * 8) * 2);
         voffW[odd] = (int)(((long)(wave * 64 + row) * p.ldw + dslot * 8) * 2);
     }
-    const int pieceA = (int)(p.lda * 16), pieceW = (int)(p.ldw * 16);      // 8 rows, bytes
+    int pieceA = (int)(p.lda * 16), pieceW = (int)(p.ldw * 16);            // 8 rows, bytes
     __amdgpu_buffer_rsrc_t rA, rW;
     Coord nc;                                      // coordinates of the tile the DMA cursor is in (= the next tile once it left this one)
     int dtile = blockIdx.x, dk = 0, dbuf = 0;
+    int dtail = 0;                                 // LORA: the cursor is in the tail stages of its tile (rA / rW / voff / piece describe T and B)
+    auto set_dma_src = [&](auto tail_c) {          // LORA: point the cursor at (T, B) or (A, W) of tile nc
+        constexpr bool TAIL = decltype(tail_c)::value;
+        const long la = TAIL ? lt.ldt : p.lda, lw = TAIL ? lt.ldb : p.ldw;
+#pragma unroll
+        for (int odd = 0; odd < 2; ++odd) {
+            const int row = lane >> 3, dslot = (lane & 7) ^ (odd * 4 + (row >> 1));
+            voffA[odd] = (wave * 64 + row) * (int)(la * 2) + dslot * 16;
+            voffW[odd] = (wave * 64 + row) * (int)(lw * 2) + dslot * 16;
+        }
+        pieceA = (int)(la * 16);
+        pieceW = (int)(lw * 16);
+        const bf16_t* Ab = TAIL ? lt.T + (long)nc.b * lt.sTb + (long)nc.m0 * lt.ldt : p.A + (long)nc.b * p.sAb + (long)nc.m0 * p.lda;
+        const bf16_t* Wb = TAIL ? lt.B + (long)nc.n0 * lt.ldb : p.W + (long)nc.n0 * p.ldw;
+        rA = __builtin_amdgcn_make_buffer_rsrc((void*)Ab, 0, (int)(min(p.M - nc.m0, BM2) * la * 2), 0x00020000);
+        rW = __builtin_amdgcn_make_buffer_rsrc((void*)Wb, 0, (int)(BN2 * lw * 2), 0x00020000);
+        dtail = TAIL;
+    };
     auto set_dma_tile = [&](int id) {
         const Coord c = coords(id);
         nc = c;
+        if constexpr (LORA) {
+            set_dma_src(std::true_type{});
+            return;
+        }
         const int Mc = c.sec ? p.M2 : p.M;
         const bf16_t* Ab = (c.sec ? p.A2 + (long)c.b * p.sAb2 : p.A + (long)c.b * p.sAb) + (long)c.m0 * p.lda;
         const bf16_t* Wb = (c.sec ? p.W2 : p.W) + (long)c.n0 * p.ldw;
@@ -556,7 +598,16 @@ __global__ __launch_bounds__(256) void gemm256w4_kernel(GemmParams p) {
         else
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rW, (__attribute__((address_space(3))) void*)dst, 16, voffW[q & 1] + (q & 7) * pieceW, dk * (BK3 * 2), 0, 0);
     };
-    auto dma_advance = [&]() { dbuf ^= 1; ++dk; };
+    auto dma_advance = [&]() {
+        dbuf ^= 1;
+        ++dk;
+        if constexpr (LORA) {
+            if (dtail && dk == ntl) {              // the tile's tail is fetched: on with its main K loop
+                set_dma_src(std::false_type{});
+                dk = 0;
+            }
+        }
+    };
     auto dma_next_tile = [&]() {                   // the cursor leaves the current tile (called once per tile, before its last two stages)
         dk = 0;
         dtile += gridDim.x;
@@ -720,6 +771,28 @@ __global__ __launch_bounds__(256) void gemm256w4_kernel(GemmParams p) {
             for (int jn = 0; jn < 8; ++jn) acc[i][jn] = f32x4{0.f, 0.f, 0.f, 0.f};
         {
             int st = 0;
+            // (LORA: the ntl tail stages lead, all of them steady since nst >= 4; after the last one the accumulators hold T B^T and take s.  s == 0
+            // clears them instead: the result is then bitwise the plain GEMM's whatever T and B hold.  A loop of its own, so that the VALU pass over
+            // the accumulators sits between two loops and not inside the one the main K loop runs in)
+            if constexpr (LORA) {
+                for (int tt = 0; tt < ntl; ++tt) kstage(std::true_type{}, true, true);
+                const float s = lt.s;
+                if (s == 0.f) {
+#pragma unroll
+                    for (int i = 0; i < 8; ++i)
+#pragma unroll
+                        for (int jn = 0; jn < 8; ++jn) acc[i][jn] = f32x4{0.f, 0.f, 0.f, 0.f};
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 8; ++i)
+#pragma unroll
+                        for (int jn = 0; jn < 8; ++jn) {      // (the compiler still gathers the 256 AGPR -> VGPR copies and spills: profiles/NOTES.md I — why the trainer does not use this kernel yet)
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) acc[i][jn][r] *= s;
+                            W4_SB();
+                        }
+                }
+            }
             for (; st + 2 < nst; ++st) kstage(std::true_type{}, true, true);
             const bool has_next = tile + (int)gridDim.x < nwg;
             dma_next_tile();
@@ -1029,4 +1102,32 @@ extern "C" int tg_gemm_bf16_qkv(const void* A1, long strideA1, const void* W1, c
         p.M2 = M2; p.Vt2 = (bf16_t*)Vt2; p.vt_ld2 = vt_ld2;
     }
     return launch<TG_EPI_BIAS>(p, stream);
+}
+
+extern "C" int tg_gemm_bf16_lora(const void* A, long lda, long strideA, const void* W, long ldw, const void* bias,
+                                 const void* T, long ldt, long strideT, const void* B, long ldb, float scale,
+                                 void* C, long ldc, long strideC, int M, int N, int K, int R, int batch, hipStream_t stream) {
+    TG_REQUIRE(A && W && T && B && C, TG_ERR_ARG, "tg_gemm_bf16_lora: null pointer");
+    TG_REQUIRE(M >= 1024 && N > 0 && batch > 0 && N % BN2 == 0 && K % BK3 == 0 && K >= 4 * BK3, TG_ERR_SHAPE,
+               "tg_gemm_bf16_lora: needs the 4-wave kernel's shapes (M >= 1024, N%%256 == 0, K%%64 == 0, K >= 256): M=%d N=%d K=%d batch=%d", M, N, K, batch);
+    TG_REQUIRE(R % BK3 == 0 && R >= BK3 && R <= 6 * BK3, TG_ERR_SHAPE, "tg_gemm_bf16_lora: the rank must be a multiple of 64 in 64..384 (R=%d)", R);
+    TG_REQUIRE(lda < (1L << 21) && ldw < (1L << 21) && ldt < (1L << 21) && ldb < (1L << 21) && lda >= K && ldw >= K && ldt >= R && ldb >= R, TG_ERR_SHAPE,
+               "tg_gemm_bf16_lora: leading dimensions must cover their rows and be < 2^21 elements");
+    TG_REQUIRE(tg_knob(TG_KNOB_GEMM_W4) != 0, TG_ERR_SHAPE, "tg_gemm_bf16_lora: only the 4-wave GEMM kernel has the low-rank tail (TG_GEMM_W4=0 is set)");
+    TG_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && ldt % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0 && strideA % 8 == 0 && strideT % 8 == 0 && strideC % 8 == 0 &&
+               tg_aligned16(A) && tg_aligned16(W) && tg_aligned16(T) && tg_aligned16(B) && tg_aligned16(C), TG_ERR_ALIGN, "tg_gemm_bf16_lora: alignment");
+    GemmParams p{};
+    p.A = (const bf16_t*)A; p.lda = lda; p.sAb = strideA;
+    p.W = (const bf16_t*)W; p.ldw = ldw;
+    p.bias = (const bf16_t*)bias;
+    p.C = (bf16_t*)C; p.ldc = ldc; p.sCb = strideC;
+    p.M = M; p.N = N; p.K = K; p.batch = batch;
+    p.group_m = K >= 8192 ? 1 : 4;
+    LoraTail lt{(const bf16_t*)T, ldt, strideT, (const bf16_t*)B, ldb, R, scale};
+    const int tiles = ((M + BM2 - 1) / BM2) * (N / BN2) * batch;
+    const int n_cu = tg_device_cus();
+    TG_DYN_LDS((gemm256w4_kernel<TG_EPI_BIAS, LoraTail>), W4_LDS_BYTES);
+    hipLaunchKernelGGL((gemm256w4_kernel<TG_EPI_BIAS, LoraTail>), dim3(tiles < n_cu ? tiles : n_cu), dim3(256), W4_LDS_BYTES, stream, p, lt);
+    TG_LAUNCH_CHECK("tg_gemm_bf16_lora");
+    return TG_OK;
 }

@@ -120,6 +120,29 @@ def gemm_act_supported(M, N, K, lda=0, ldw=0):
             and L.debug_get("TG_GEMM_W4") != 0)                                                            # the knob the library dispatches on, not the environment
 
 
+def gemm_lora_supported(M, N, K, R, lda=0, ldw=0, ldt=0, ldb=0):
+    """Shapes tg_gemm_bf16_lora takes (the 4-wave GEMM kernel's, and a rank that is a multiple of 64 in 64..384).  Elsewhere: gemm(EPI_BIAS) + the
+    accumulating gemm(EPI_BIAS_GATE_RES) with a gate table that holds the scale."""
+    return (M >= 1024 and N % 256 == 0 and K % 64 == 0 and K >= 256 and R % 64 == 0 and 64 <= R <= 384 and max(lda, ldw, ldt, ldb, K) < (1 << 21)
+            and L.debug_get("TG_GEMM_W4") != 0)
+
+
+def gemm_lora(a, w, bias, t, b, scale, out):
+    """out = bf16(a @ w.T + bias + scale * (t @ b.T)) in one launch (tg_gemm_bf16_lora): a [.., M, K], w [N, K], t [.., M, R] (the adapter's down-projection),
+    b [N, R] (lora_B), scale a Python float (applied in fp32), out [.., M, N]; views with row / batch strides allowed.  Shapes: gemm_lora_supported."""
+    _chk(a, "a"); _chk(w, "w"); _chk(t, "t"); _chk(b, "b"); _chk(out, "out")
+    B, M, K, lda, sa = _bmk(a)
+    Bt, Mt, R, ldt, st = _bmk(t)
+    Bo, Mo, N, ldc, sc = _bmk(out)
+    if (B, M) != (Bo, Mo) or (B, M) != (Bt, Mt) or w.shape != (N, K) or b.shape != (N, R):
+        raise ValueError(f"gemm_lora: shape mismatch a{tuple(a.shape)} w{tuple(w.shape)} t{tuple(t.shape)} b{tuple(b.shape)} out{tuple(out.shape)}")
+    if bias is not None:
+        _chk(bias, "bias")
+    L.check(_launch(f"gemm_lora_M{M}_N{N}_K{K}_R{R}", L.load().tg_gemm_bf16_lora, _p(a), lda, sa, _p(w), w.stride(0), _p(bias), _p(t), ldt, st, _p(b), b.stride(0),
+                    float(scale), _p(out), ldc, sc, M, N, K, R, B, _stream()), "tg_gemm_bf16_lora")
+    return out
+
+
 def gemm_pair(a1, w1, bias1, out1, a2, w2, bias2, out2, epilogue=L.EPI_BIAS):
     """out1 = epi(a1 @ w1^T + bias1) and out2 = epi(a2 @ w2^T + bias2) in one launch (tg_gemm_bf16_pair): same N, K, batch, leading
     dimensions; [B, M, K] activations with M >= 1024."""

@@ -8,7 +8,16 @@ step (clip + AdamW8bit over 5.57 B parameters), the peak device memory, the tran
 step_mfma_frac = TFLOP / time / 2.5 PFLOP/s.  Prints one JSON line; --out also writes it to a file.  The recompute schedule runs on the weights the
 first schedule's optimizer step left (random weights after one AdamW step: its losses differ; the times do not depend on the values).
 
-    python tools/bench_t2to_train.py [--layers 42] [--out profiles/t2to_train_bench.json]"""
+    python tools/bench_t2to_train.py [--layers 42] [--out profiles/t2to_train_bench.json]
+
+--lora: adapter-only training (transformer_trainable_modules [], a rank-128 adapter on to_q | to_k | to_v | to_out.0, the base frozen) against full
+fine-tuning IN THE SAME PROCESS, alternating, `--rounds` rounds (median reported): ms per micro-step (forward + masked loss + backward + gradient accumulation,
+no optimizer step), peak device memory, arena bytes; the adapter-only micro-step with the low-rank tail folded into the projection GEMMs (kernels.gemm_lora)
+and in the two-launch form; and the kernel A/B itself, gemm_lora against gemm + the accumulating tail GEMM at [28 326, 3072] -> 9216, R = 128 and at the shapes
+the trainer launches.  --parent-json: a result line of this tool run from the PARENT commit on the same box just before (its full fine-tuning micro-step is
+copied into the record next to this tree's).
+
+    python tools/bench_t2to_train.py --lora [--parent-json FILE] [--out profiles/t2to_lora_bench.json]"""
 import argparse
 import json
 import os
@@ -66,6 +75,126 @@ def micro_step_flops(B, N, D, layers, recomputed):
     return layers * (fwd + bwd) + recomputed * fwd
 
 
+def _median(v):
+    v = sorted(v)
+    return v[len(v) // 2]
+
+
+def kernel_ab(M, N, Kd, R, rounds, reps=8, dev="cuda"):
+    """gemm_lora against the two-launch form (gemm EPI_BIAS + the accumulating gemm EPI_BIAS_GATE_RES with the scale in a gate table), interleaved: per round
+    `reps` back-to-back launches of each form between two events; the median round of each."""
+    from tokensgen_amd import kernels as K
+    from tokensgen_amd import lib as L
+    g = torch.Generator(device=dev).manual_seed(3)
+    rnd = lambda *s, sc=1.0: (torch.randn(*s, device=dev, generator=g) * sc).to(torch.bfloat16)
+    x, w, b, t, bm = rnd(1, M, Kd), rnd(N, Kd, sc=0.02), rnd(N), rnd(1, M, R), rnd(N, R, sc=0.02)
+    out = torch.empty(1, M, N, dtype=torch.bfloat16, device=dev)
+    tab = K.GroupTable(torch.full((1, 1, N), 0.5, dtype=torch.bfloat16, device=dev), torch.zeros(M, dtype=torch.uint8, device=dev), [0], [0], [0], [0])
+
+    def fused():
+        K.gemm_lora(x, w, b, t, bm, 0.5, out)
+
+    def two():
+        K.gemm(x, w, b, out, L.EPI_BIAS)
+        K.gemm(t, bm, None, out, L.EPI_BIAS_GATE_RES, residual=out, gate=tab)
+
+    def plain():
+        K.gemm(x, w, b, out, L.EPI_BIAS)
+    ms = {"gemm_lora": [], "two_launch": [], "plain_gemm": []}
+    for fn in (fused, two, plain):
+        fn()
+    for _ in range(rounds):
+        for name, fn in (("gemm_lora", fused), ("two_launch", two), ("plain_gemm", plain)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(reps):
+                fn()
+            e1.record()
+            e1.synchronize()
+            ms[name].append(e0.elapsed_time(e1) / reps)
+    return dict(M=M, N=N, K=Kd, R=R, rounds=ms, gemm_lora_ms=_median(ms["gemm_lora"]), two_launch_ms=_median(ms["two_launch"]),
+                plain_gemm_ms=_median(ms["plain_gemm"]), gemm_lora_over_two_launch=_median(ms["gemm_lora"]) / _median(ms["two_launch"]))
+
+
+def lora_ab(a):
+    """Adapter-only against full fine-tuning, alternating in one process (see the module docstring)."""
+    from oracle import scheduler_ref as S
+    from tokensgen_amd import lora
+    from tokensgen_amd.train_t2to import T2ToTrainer, T2ToTrainStep, make_arena, t2to_rope
+    dev = "cuda"
+    D, H, te, Nt, text_dim = 3072, 48, 512, 226, 4096
+    B, Fr = a.batch, 4 * a.chunks
+    N = Nt + Fr * 96
+    res = dict(metric="T2To micro-step: adapter-only (rank-128 LoRA on to_q|to_k|to_v|to_out.0, frozen base) vs full fine-tuning, same process, alternating",
+               device=torch.cuda.get_device_name(0), batch=B, latent_frames=Fr, tokens_per_item=N, layers=a.layers, width=D, rounds=a.rounds)
+    res["kernel_ab"] = [kernel_ab(B * N, 3 * D, D, 128, a.rounds),                                   # the issue's shape: the whole fused q|k|v projection
+                        kernel_ab(B * N, D, D, 128, a.rounds),                                       # what the trainer launches: a third / to_out (forward), to_out's dgrad
+                        kernel_ab(B * N, D, 3 * D, 384, a.rounds)]                                   # ... and the q|k|v input gradient (K = 3D, R = 3r)
+    print(json.dumps(res["kernel_ab"]), file=sys.stderr, flush=True)
+    sd = synthetic_state_dict(D, H, a.layers, te, text_dim, dev)
+    yaml = dict(optimizer="adamw", use_8bit_adam=True, learning_rate=3e-4, adam_beta1=0.9, adam_beta2=0.95, adam_epsilon=1e-8,
+                adam_weight_decay=1e-4, max_grad_norm=1.0)
+    _, ac = S.alphas_cumprod()
+    acp = torch.as_tensor(ac, dtype=torch.float32)
+    full = T2ToTrainer(sd, H, a.layers)
+    arena_f, opt_f = make_arena(full, yaml)
+    lcfg = lora.LoraConfig(rank=128, lora_alpha=64)
+    ad = lora.init_adapter(lcfg, sd, torch.Generator().manual_seed(2), device=dev)
+    g = torch.Generator(device=dev).manual_seed(1)
+    for k in ad:                                                                                     # a trained adapter: B is not zero
+        if k.endswith("lora_B.weight"):
+            ad[k] = (torch.randn(ad[k].shape, device=dev, generator=g) * 0.02).to(torch.bfloat16)
+    lo = T2ToTrainer({**sd, **ad}, H, a.layers, trainable_modules=[], lora=lcfg)                      # the base tensors are the full trainer's arena views: one copy
+    arena_l, opt_l = make_arena(lo, yaml)
+    never = 1 << 30                                                                                  # no window ends: micro-steps only
+    steps = {"full": T2ToTrainStep(full, arena_f, opt_f, acp, accumulation_steps=never), "lora": T2ToTrainStep(lo, arena_l, opt_l, acp, accumulation_steps=never)}
+    rope = t2to_rope(Fr, device=dev)
+    x0 = torch.randn(B, Fr, 16, 8, 12, device=dev, generator=g).to(torch.bfloat16)
+    noise, text = torch.randn_like(x0), torch.randn(B, Nt, text_dim, device=dev, generator=g).to(torch.bfloat16)
+    ts = torch.tensor([37, 512, 901, 250, 700, 90][:B])
+
+    def micro(which, fused_tail=True):
+        lo.fused_tail = fused_tail                                                                   # (the blocks keep their frozen weights' transposes across the switch)
+        tr = steps[which].tr
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        t0 = time.perf_counter()
+        loss, _ = steps[which].micro_step(noise, ts, text, rope, [a.chunks] * B, model_input=x0)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, torch.cuda.max_memory_allocated() / 1e9, tr.blocks_kept, float(loss)
+    modes = (("full", "full", True), ("lora_gemm_lora", "lora", True), ("lora_two_launch", "lora", False))
+    for _, which, ft in modes:                                                                       # warm-up: workspaces, the frozen weights' kept transposes
+        micro(which, ft)
+    runs = {m: [] for m, _, _ in modes}
+    for r in range(a.rounds):
+        for m, which, ft in modes:
+            runs[m].append(micro(which, ft))
+            print(json.dumps({m: runs[m][-1]}), file=sys.stderr, flush=True)
+    for m in runs:
+        res[m] = dict(ms_per_micro_step=_median([x[0] for x in runs[m]]), ms_rounds=[x[0] for x in runs[m]], peak_mem_gb=max(x[1] for x in runs[m]),
+                      blocks_kept=runs[m][-1][2], loss=runs[m][-1][3])
+    only_full = (arena_f.grad.numel() * 4 + sum(t.numel() * t.element_size() for t in vars(opt_f).values() if torch.is_tensor(t))) / 1e9
+    res["arena"] = dict(full_params=arena_f.param.numel(), full_param_bytes=arena_f.param.numel() * 2, full_grad_bytes=arena_f.grad.numel() * 4,
+                        lora_params=arena_l.param.numel(), lora_param_bytes=arena_l.param.numel() * 2, lora_grad_bytes=arena_l.grad.numel() * 4)
+    res["note_memory"] = ("both trainers are resident: the adapter-only peaks include the full trainer's gradient arena and optimizer state, "
+                          f"{only_full:.1f} GB that an adapter-only process does not hold (the bf16 parameter arena doubles as the frozen base)")
+    res["full_trainer_only_state_gb"] = only_full
+    res["lora_over_full"] = res["lora_gemm_lora"]["ms_per_micro_step"] / res["full"]["ms_per_micro_step"]
+    res["gemm_lora_over_two_launch_micro_step"] = res["lora_gemm_lora"]["ms_per_micro_step"] / res["lora_two_launch"]["ms_per_micro_step"]
+    if a.parent_json and os.path.exists(a.parent_json):
+        with open(a.parent_json) as f:
+            par = json.loads(f.read().strip().splitlines()[-1])
+        res["parent_commit_full_fine_tuning"] = {k: par[k] for k in ("kept", "recompute", "layers", "batch", "tokens_per_item", "accumulation_steps") if k in par}
+        res["full_over_parent_kept"] = res["full"]["ms_per_micro_step"] / par["kept"]["ms_per_micro_step"]
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--layers", type=int, default=42)
@@ -73,7 +202,12 @@ def main():
     ap.add_argument("--chunks", type=int, default=24)
     ap.add_argument("--accum", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--lora", action="store_true", help="adapter-only vs full fine-tuning, alternating (see the module docstring)")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--parent-json", default=None)
     a = ap.parse_args()
+    if a.lora:
+        return lora_ab(a)
     from oracle import scheduler_ref as S
     from tokensgen_amd.train_t2to import T2ToTrainer, T2ToTrainStep, make_arena, t2to_rope
     dev = "cuda"
