@@ -103,6 +103,13 @@ int tg_gemm_bf16_lora(const void* A, long lda, long strideA, const void* W, long
                       const void* T, long ldt, long strideT, const void* B, long ldb, float scale,
                       void* C, long ldc, long strideC, int M, int N, int K, int R, int batch, hipStream_t stream);
 
+/* Which kernel tg_gemm_bf16 with TG_EPI_BIAS and batch 1 launches for this shape NOW (the TG_GEMM_W4 knob included): 0 the 128x128 tile, 1 the 8-wave
+ * 256x256 kernel, 2 the 4-wave 256x256 kernel; the negative error code for a shape tg_gemm_bf16 refuses.  A pure host query (no launch, no device needed).
+ * The 4-wave shape rule is restated at the epilogue enum and at the qkv and lora entries above; this answer is the authoritative one: 2 is what
+ * TG_EPI_BIAS_KEEP_GELU / _MUL_GELU_GRAD, tg_gemm_bf16_qkv and tg_gemm_bf16_lora need (each with its own further conditions), >= 1 for both M what
+ * tg_gemm_bf16_pair needs. */
+long tg_gemm_kernel(int M, int N, int K, long lda, long ldw);
+
 /* y = LayerNorm(x; w, b, eps) * (1 + scale[g]) + shift[g], g = group of the token.  One pass, fp32 stats.
  * modulate == 0: plain affine LayerNorm (norm_final, cogvideox_transformer_3d.py:741).
  * Replaces normalization.py:441-460 (CogVideoXLayerNormZero), :477-488 (VIP), :70-92 (AdaLayerNorm).

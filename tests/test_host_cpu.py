@@ -403,3 +403,125 @@ def test_conv_plan_table():
     assert len(got) == len(want)
     for g, w in zip(got, want):
         assert g == w
+
+
+GEMM_PLAN_TABLE = """
+    plain 28326x3072->9216: k256w4 grid 256 block 256 lds 150784 group_m 4
+    plain 28326x12288->3072: k256w4 grid 256 block 256 lds 150784 group_m 1
+    plain 1024x8128->256: k256w4 grid 4 block 256 lds 150784 group_m 4
+    plain 1024x8192->256: k256w4 grid 4 block 256 lds 150784 group_m 1
+    plain 1023x256->256: k128 grid 16 block 256 lds 65536 group_m 0
+    plain 1024x256->256: k256w4 grid 4 block 256 lds 150784 group_m 4
+    plain 1024x256->384: k128 grid 24 block 256 lds 65536 group_m 0
+    plain 1024x192->256: k256w8 grid 4 block 512 lds 131072 group_m 4
+    plain 1024x256->256 w4=0: k256w8 grid 4 block 512 lds 131072 group_m 4
+    plain 1024x256->256 lda 2^21-8: k256w4 grid 4 block 256 lds 150784 group_m 4
+    plain 1024x256->256 lda 2^21: k256w8 grid 4 block 512 lds 131072 group_m 4
+    plain 1024x256->256 ldw 2^21: k256w8 grid 4 block 512 lds 131072 group_m 4
+    plain 2048x256->512 batch 2: k256w4 grid 32 block 256 lds 150784 group_m 4
+    plain 65280x256->256 (255 tiles): k256w4 grid 255 block 256 lds 150784 group_m 4
+    plain 65536x256->256 (256 tiles): k256w4 grid 256 block 256 lds 150784 group_m 4
+    plain 65537x256->256 (257 tiles): k256w4 grid 256 block 256 lds 150784 group_m 4
+    plain 1x512->18432: k128 grid 144 block 256 lds 65536 group_m 0
+    plain 300x64->128 batch 3: k128 grid 9 block 256 lds 65536 group_m 0
+    plain gate_res 1024x256->256: k256w4 grid 4 block 256 lds 150784 group_m 4
+    plain gate_res 1000x256->256: k128 grid 16 block 256 lds 65536 group_m 0
+    plain keep_gelu 1024x256->256: k256w4 grid 4 block 256 lds 150784 group_m 4
+    plain gelu_grad 1024x256->256: k256w4 grid 4 block 256 lds 150784 group_m 4
+    pair 1024+1280 x256->256: k256w4 grid 9 block 256 lds 150784 group_m 4
+    pair 1024+1280 x64->256: k256w8 grid 9 block 512 lds 131072 group_m 4
+    pair 1024+1280 x256->256 w4=0: k256w8 grid 9 block 512 lds 131072 group_m 4
+    pair silu 1024+1280 x256->256: k256w4 grid 9 block 256 lds 150784 group_m 4
+    qkv 1024x256->768 v_col0 512: k256w4 grid 12 block 256 lds 150784 group_m 4
+    qkv 1024+1280 x256->768 v_col0 512: k256w4 grid 27 block 256 lds 150784 group_m 4
+    lora 1024x256->256 R 64: k256w4 grid 4 block 256 lds 150784 group_m 4
+    lora 1024x256->256 R 384: k256w4 grid 4 block 256 lds 150784 group_m 4
+    lora 1024x8192->256 R 64: k256w4 grid 4 block 256 lds 150784 group_m 1
+    refused: plain M = 0: error -2: tg_gemm_bf16: bad dims M=0 N=128 K=64 batch=1
+    refused: plain N = 100: error -2: tg_gemm_bf16: need N%128==0 and K%64==0 (N=100 K=64)
+    refused: plain K = 96: error -2: tg_gemm_bf16: need N%128==0 and K%64==0 (N=128 K=96)
+    refused: plain epilogue 6: error -1: tg_gemm_bf16: unknown epilogue 6
+    plain 2147483391x64->65536 (2^31 - 256 tiles): k256w8 grid 256 block 512 lds 131072 group_m 4
+    refused: plain 2147483647x64->65536 (2^31 tiles): error -2: tg_gemm_bf16: too many tiles
+    refused: plain keep_gelu M = 512: error -2: tg_gemm_bf16: the keep-GELU / GELU-grad epilogues exist in the 4-wave kernel only (M >= 1024, N%256 == 0, K >= 256)
+    refused: plain keep_gelu K = 192: error -2: tg_gemm_bf16: the keep-GELU / GELU-grad epilogues exist in the 4-wave kernel only (M >= 1024, N%256 == 0, K >= 256)
+    refused: plain keep_gelu N = 384: error -2: tg_gemm_bf16: the keep-GELU / GELU-grad epilogues exist in the 4-wave kernel only (M >= 1024, N%256 == 0, K >= 256)
+    refused: plain keep_gelu w4=0: error -2: tg_gemm_bf16: the keep-GELU / GELU-grad epilogues exist in the 4-wave kernel only (M >= 1024, N%256 == 0, K >= 256)
+    refused: plain gelu_grad M = 512: error -2: tg_gemm_bf16: the keep-GELU / GELU-grad epilogues exist in the 4-wave kernel only (M >= 1024, N%256 == 0, K >= 256)
+    refused: plain gelu_grad K = 192: error -2: tg_gemm_bf16: the keep-GELU / GELU-grad epilogues exist in the 4-wave kernel only (M >= 1024, N%256 == 0, K >= 256)
+    refused: plain gelu_grad N = 384: error -2: tg_gemm_bf16: the keep-GELU / GELU-grad epilogues exist in the 4-wave kernel only (M >= 1024, N%256 == 0, K >= 256)
+    refused: plain gelu_grad w4=0: error -2: tg_gemm_bf16: the keep-GELU / GELU-grad epilogues exist in the 4-wave kernel only (M >= 1024, N%256 == 0, K >= 256)
+    refused: pair M2 = 1023: error -2: tg_gemm_bf16_pair: both problems must be 256^2-kernel shapes (M >= 1024, N%256 == 0, K%64 == 0)
+    refused: pair N = 384: error -2: tg_gemm_bf16_pair: both problems must be 256^2-kernel shapes (M >= 1024, N%256 == 0, K%64 == 0)
+    refused: pair epilogue 3: error -1: tg_gemm_bf16_pair: bias / GELU / SiLU epilogues only
+    refused: qkv K = 192: error -2: tg_gemm_bf16_qkv: needs the 4-wave kernel's shapes (M >= 1024, N%256 == 0, K%64 == 0, K >= 256)
+    refused: qkv M = 1023: error -2: tg_gemm_bf16_qkv: needs the 4-wave kernel's shapes (M >= 1024, N%256 == 0, K%64 == 0, K >= 256)
+    refused: qkv M2 = 512: error -2: tg_gemm_bf16_qkv: needs the 4-wave kernel's shapes (M >= 1024, N%256 == 0, K%64 == 0, K >= 256)
+    refused: qkv v_col0 = 0: error -2: tg_gemm_bf16_qkv: v_col0 must be a multiple of 256 inside (0, N)
+    refused: qkv v_col0 = N: error -2: tg_gemm_bf16_qkv: v_col0 must be a multiple of 256 inside (0, N)
+    refused: qkv v_col0 = 384: error -2: tg_gemm_bf16_qkv: v_col0 must be a multiple of 256 inside (0, N)
+    refused: qkv vt_ld = 1000: error -2: tg_gemm_bf16_qkv: vt_ld must be a multiple of 64 and >= M
+    refused: qkv vt_ld = 960: error -2: tg_gemm_bf16_qkv: vt_ld must be a multiple of 64 and >= M
+    refused: qkv lda = 2^21: error -2: tg_gemm_bf16_qkv: leading dimensions must be < 2^21 elements
+    refused: qkv w4=0: error -1: tg_gemm_bf16_qkv: only the 4-wave GEMM kernel has the V^T epilogue (TG_GEMM_W4=0 is set)
+    refused: lora M = 1023: error -2: tg_gemm_bf16_lora: needs the 4-wave kernel's shapes (M >= 1024, N%256 == 0, K%64 == 0, K >= 256): M=1023 N=256 K=256 batch=1
+    refused: lora R = 32: error -2: tg_gemm_bf16_lora: the rank must be a multiple of 64 in 64..384 (R=32)
+    refused: lora R = 96: error -2: tg_gemm_bf16_lora: the rank must be a multiple of 64 in 64..384 (R=96)
+    refused: lora R = 448: error -2: tg_gemm_bf16_lora: the rank must be a multiple of 64 in 64..384 (R=448)
+    refused: lora ldt = 56: error -2: tg_gemm_bf16_lora: leading dimensions must cover their rows and be < 2^21 elements
+    refused: lora ldb = 2^21: error -2: tg_gemm_bf16_lora: leading dimensions must cover their rows and be < 2^21 elements
+    refused: lora w4=0: error -2: tg_gemm_bf16_lora: only the 4-wave GEMM kernel has the low-rank tail (TG_GEMM_W4=0 is set)
+"""
+
+
+def test_gemm_plan_table():
+    """tokensgen_amd/csrc/gemm_plan.h: which of the three GEMM kernels, grid, block, LDS bytes and group_m the four entry points of gemm.hip launch for a shape, and
+    which shapes they refuse with which code and text, as a pure host function printed by tests/gemm_plan_table (tests/csrc/gemm_plan_table.cpp: the cases; 256 CUs;
+    a case is named M x K -> N).  The workload's block projections, then a case on each side of every threshold: M against 1024, N a multiple of 128 only, K against
+    256 and 8192, the knob, the leading dimensions against 2^21, the tiles against the CU count and against 2^31; then one refused shape per message on each side of its
+    threshold.  TG_GEMM_W4 = 0 where only the 4-wave kernel will do is -1 from the qkv entry and -2 from the lora entry and the activation epilogues: the codes are ABI."""
+    import subprocess
+    exe = os.path.join(ROOT, "tests", "gemm_plan_table")
+    assert os.path.exists(exe), "build first: python -c 'import __graft_entry__ as g; g.build()'"
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr[-2000:]
+    got, want = r.stdout.splitlines(), [ln.strip() for ln in GEMM_PLAN_TABLE.strip().splitlines()]
+    assert len(got) == len(want)
+    for g, w in zip(got, want):
+        assert g == w
+
+
+def test_gemm_supported_predicates():
+    """kernels.gemm_{act,lora,qkv,pair}_supported ask the library (tg_gemm_kernel: gemm_plan.h with the live TG_GEMM_W4 knob) instead of restating its rule.  The
+    values below are what the hand-written conditions they replace answered, with the knob at 1 and at 0: the workload's shapes, M at 1023 / 1024, K at 192 / 256,
+    N = 384, the rank at 32 / 64 / 384 / 448, a leading dimension at 2^21 - 8 / 2^21.  (act, lora: M, N, K[, R][, lda, ldw[, ldt, ldb]]; qkv: M, N, K, v_col0; pair:
+    M1, M2, N, K.)"""
+    from tokensgen_amd import kernels as K, lib as L
+    P = 1 << 21
+    T, F = True, False
+    table = {       # helper: [(arguments, answer with TG_GEMM_W4 = 1, answer with TG_GEMM_W4 = 0)]
+        K.gemm_act_supported: [
+            ((28326, 12288, 3072), T, F), ((28326, 3072, 12288), T, F), ((17550, 12288, 3072), T, F), ((17776, 12288, 3072), T, F), ((1023, 256, 256), F, F),
+            ((1024, 256, 256), T, F), ((1024, 256, 192), F, F), ((1024, 384, 256), F, F), ((300, 256, 256), F, F), ((1024, 256, 256, P - 8, P - 8), T, F),
+            ((1024, 256, 256, P, 256), F, F), ((1024, 256, 256, 256, P), F, F), ((1024, 100, 256), F, F), ((1024, 256, 96), F, F)],
+        K.gemm_lora_supported: [
+            ((28326, 9216, 3072, 128), T, F), ((28326, 3072, 3072, 64), T, F), ((17550, 3072, 3072, 64), T, F), ((1024, 256, 256, 64), T, F),
+            ((1023, 256, 256, 64), F, F), ((1024, 256, 192, 64), F, F), ((1024, 384, 256, 64), F, F), ((1024, 256, 256, 32), F, F), ((1024, 256, 256, 384), T, F),
+            ((1024, 256, 256, 448), F, F), ((1024, 256, 256, 96), F, F), ((1024, 256, 256, 64, P - 8, P - 8, P - 8, P - 8), T, F),
+            ((1024, 256, 256, 64, P, 256, 64, 64), F, F), ((1024, 256, 256, 64, 256, 256, P, 64), F, F), ((1024, 256, 256, 64, 256, 256, 64, P), F, F)],
+        K.gemm_qkv_supported: [
+            ((17776, 9216, 3072, 6144), T, F), ((28326, 9216, 3072, 6144), T, F), ((17550, 9216, 3072, 6144), T, F), ((1024, 768, 256, 512), T, F),
+            ((1023, 768, 256, 512), F, F), ((1024, 768, 192, 512), F, F), ((1024, 384, 256, 256), F, F), ((1024, 768, 256, 384), F, F), ((1024, 768, 256, 256), T, F),
+            ((300, 384, 128, 256), F, F)],
+        K.gemm_pair_supported: [      # the pair entry takes either 256x256 kernel: the knob does not matter
+            ((17776, 28326, 9216, 3072), T, T), ((17550, 17776, 9216, 3072), T, T), ((1024, 1280, 768, 256), T, T), ((1023, 1280, 768, 256), F, F),
+            ((1024, 1280, 384, 256), F, F), ((1024, 1280, 768, 192), T, T), ((1024, 1024, 256, 64), T, T), ((300, 330, 384, 128), F, F)],
+    }
+    for knob in (1, 0):
+        old = L.debug_set("TG_GEMM_W4", knob)
+        try:
+            for fn, cases in table.items():
+                for case in cases:
+                    assert fn(*case[0]) is case[2 - knob], (fn.__name__, case[0], knob)
+        finally:
+            L.debug_set("TG_GEMM_W4", old)

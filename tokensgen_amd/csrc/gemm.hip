@@ -19,13 +19,12 @@
 
 #include <type_traits>
 #include "common.h"
+#include "gemm_plan.h"
 #include "tokensgen_hip.h"
 
 namespace {
 
-constexpr int BM = 128, BN = 128, BK = 64;
-constexpr int TILE_BYTES = BM * BK * 2;          // 16 KiB per operand tile
-constexpr int STAGE_BYTES = 2 * TILE_BYTES;      // A + W
+using namespace gemm_cfg;                        // the tile and LDS sizes: gemm_plan.h
 #ifndef TG_GROUP_M
 #define TG_GROUP_M 8
 #endif
@@ -47,7 +46,7 @@ struct GemmParams {
     // delivered in the [head][64][keys] layout tg_attention_fwd reads
     bf16_t* Vt; bf16_t* Vt2; long vt_ld, vt_ld2; int vt_col0;
     int tiles1;                                   // tiles of the first problem
-    int group_m;                                  // m-tiles per n sweep of the 256^2 kernel's tile order (see launch())
+    int group_m;                                  // m-tiles per n sweep of the 256^2 kernel's tile order (gemm_plan.h)
 };
 
 // low-rank tail of tg_gemm_bf16_lora (4-wave kernel only): C = bf16(A W^T + bias + s (T B^T)), T [batch][M][R], B [N][R].  The tail is R / 64
@@ -232,10 +231,6 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmParams p) {
 //   complete one full phase before its first reader, and the barrier that follows publishes it.  The ring slot of stage
 //   s+3 is that of stage s-1, whose last reader (group 1, LOAD phase 1) finished two intervals before the first overwrite.
 // ================================================================================================
-constexpr int BM2 = 256, BN2 = 256, BK2 = 32, NS2 = 4;
-constexpr int OPER2_BYTES = BM2 * BK2 * 2;       // 16 KiB per operand per stage
-constexpr int STAGE2_BYTES = 2 * OPER2_BYTES;    // 32 KiB
-constexpr int RING2_BYTES = NS2 * STAGE2_BYTES;  // 128 KiB
 
 template <int EPI>
 __global__ __launch_bounds__(512) void gemm256_kernel(GemmParams p) {
@@ -488,14 +483,6 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmParams p) {
 //     slot 93       vmcnt(pieces issued so far) + s_barrier: stage s+1 landed everywhere; then (every 2nd slot) reads of set 0 of s+1
 //   The stage stream runs across output tiles (persistent): the last two stages of a tile fetch the first two of the next.
 // ================================================================================================
-constexpr int BK3 = 64;
-constexpr int OPER3_BYTES = 256 * BK3 * 2;       // 32 KiB per operand per stage
-constexpr int STAGE3_BYTES = 2 * OPER3_BYTES;    // 64 KiB
-constexpr int W4_STG_OFF = 2 * STAGE3_BYTES;     // epilogue staging behind the two stages
-constexpr int W4_BIAS_OFF = W4_STG_OFF + 4 * 4096;   // 256 B of bias per wave
-constexpr int W4_TOK_OFF = W4_BIAS_OFF + 4 * 256;    // gated-residual epilogue: group id of this wave's 128 rows, one dword each
-constexpr int W4_GTAB_OFF = W4_TOK_OFF + 4 * 512;    // ... and the gate-row element offset of every group (16 dwords per wave)
-constexpr int W4_LDS_BYTES = W4_GTAB_OFF + 4 * 64;
 
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -968,109 +955,101 @@ __global__ __launch_bounds__(256) void gemm256w4_kernel(GemmParams p, Tail... ta
 #undef W4_DSR
 }
 
-template <int EPI>
-int launch(GemmParams p, hipStream_t stream) {
-    if (p.M >= 1024 && p.N % BN2 == 0) {   // large-M shapes: 256^2 ping-pong kernel
-        const int tiles2 = (((p.M + BM2 - 1) / BM2) + (p.A2 ? (p.M2 + BM2 - 1) / BM2 : 0)) * (p.N / BN2) * p.batch;
-        // tile order: groups of group_m m-tiles x all n-tiles, m fastest; the 32 tiles resident on one XCD then share group_m A panels and
-        // 32/group_m W panels.  A (activations) is the big, XCD-private operand, W (weights) is shared by every XCD through the
-        // Infinity Cache, so small groups win: measured sum over the four block GEMMs 7.61 (8) / 7.48 (4) / 7.53 (6) / 7.62 (2) ms,
-        // and for K = 12288 (6.3 MB per A panel) a single m-tile per group is another 3 % faster (2.31 vs 2.34 vs 2.40 ms)
-        p.group_m = p.K >= 8192 ? 1 : 4;
-        const int n_cu = tg_device_cus();
-        const dim3 grid2(tiles2 < n_cu ? tiles2 : n_cu);
-        const bool w4 = tg_knob(TG_KNOB_GEMM_W4) != 0;     // 0 (cross-check tests): the 8-wave kernel for every shape
-        if (w4 && p.K >= 4 * BK3 && p.lda < (1L << 21) && p.ldw < (1L << 21)) {   // 32-bit buffer offsets: 256 rows * ld * 2 B < 2^31
-            TG_DYN_LDS(gemm256w4_kernel<EPI>, W4_LDS_BYTES);
-            hipLaunchKernelGGL(gemm256w4_kernel<EPI>, grid2, dim3(256), W4_LDS_BYTES, stream, p);
-            TG_LAUNCH_CHECK("tg_gemm_bf16(256w4)");
-            return TG_OK;
-        }
-        TG_DYN_LDS(gemm256_kernel<EPI>, RING2_BYTES);
-        hipLaunchKernelGGL(gemm256_kernel<EPI>, grid2, dim3(512), RING2_BYTES, stream, p);
-        TG_LAUNCH_CHECK("tg_gemm_bf16(256)");
-        return TG_OK;
+// One launch for every entry point: gemm_plan() (gemm_plan.h) has named the kernel, grid, block, LDS bytes and tile order.  The activation epilogues (EPI 4, 5)
+// and the LoRA tail exist in the 4-wave kernel only: the other two kernels are never instantiated for them.
+#define GEMM_LAUNCH(KERNEL, NAME, ...)                                                             \
+    do {                                                                                           \
+        TG_DYN_LDS(KERNEL, pl.lds);                                                                \
+        hipLaunchKernelGGL(KERNEL, dim3(pl.grid), dim3(pl.block), pl.lds, stream, __VA_ARGS__);   \
+        TG_LAUNCH_CHECK(NAME);                                                                     \
+        return TG_OK;                                                                              \
+    } while (0)
+template <int EPI, typename... Tail>
+int launch_plan(const GemmPlan& pl, GemmParams p, hipStream_t stream, Tail... tail) {
+    constexpr bool ALL_KERNELS = EPI <= TG_EPI_BIAS_GATE_RES && sizeof...(Tail) == 0;
+    p.group_m = pl.group_m;
+    switch (pl.kernel) {
+        case GEMM_K256W4: GEMM_LAUNCH((gemm256w4_kernel<EPI, Tail...>), "tg_gemm_bf16(256w4)", p, tail...);
+        case GEMM_K256W8:
+            if constexpr (ALL_KERNELS) GEMM_LAUNCH(gemm256_kernel<EPI>, "tg_gemm_bf16(256)", p);
+            break;
+        case GEMM_K128:
+            if constexpr (ALL_KERNELS) GEMM_LAUNCH(gemm_bf16_kernel<EPI>, "tg_gemm_bf16", p);
+            break;
     }
-    const int tiles = ((p.M + BM - 1) / BM) * (p.N / BN) * p.batch;
-    TG_DYN_LDS(gemm_bf16_kernel<EPI>, 2 * STAGE_BYTES);
-    hipLaunchKernelGGL(gemm_bf16_kernel<EPI>, dim3(tiles), dim3(256), 2 * STAGE_BYTES, stream, p);
-    TG_LAUNCH_CHECK("tg_gemm_bf16");
-    return TG_OK;
+    return tg_set_error(TG_ERR_ARG, "tg_gemm_bf16: epilogue %d has no kernel %d", EPI, (int)pl.kernel);      // not reached: the plan refuses these shapes
 }
+#undef GEMM_LAUNCH
 
-}  // namespace
+GemmPlan plan(const GemmShape& s) { return gemm_plan(s, tg_knob(TG_KNOB_GEMM_W4) != 0, tg_device_cus()); }
 
-extern "C" int tg_gemm_bf16(const void* A, long lda, long strideA, const void* W, long ldw, const void* bias,
-                            void* C, long ldc, long strideC, int M, int N, int K, int batch, int epilogue,
-                            const void* R, long ldr, long strideR, const tg_group_table* gate, hipStream_t stream) {
-    TG_REQUIRE(A && W && C, TG_ERR_ARG, "tg_gemm_bf16: null pointer");
-    TG_REQUIRE(M > 0 && N > 0 && K > 0 && batch > 0, TG_ERR_SHAPE, "tg_gemm_bf16: bad dims M=%d N=%d K=%d batch=%d", M, N, K, batch);
-    TG_REQUIRE(N % BN == 0 && K % BK == 0, TG_ERR_SHAPE, "tg_gemm_bf16: need N%%128==0 and K%%64==0 (N=%d K=%d)", N, K);
-    TG_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && ldc % 8 == 0 && strideA % 8 == 0 && strideC % 8 == 0, TG_ERR_ALIGN,
-               "tg_gemm_bf16: leading dimensions must keep 16-byte (A, W) / 8-byte (C) alignment");
-    TG_REQUIRE(tg_aligned16(A) && tg_aligned16(W) && tg_aligned16(C), TG_ERR_ALIGN, "tg_gemm_bf16: unaligned base pointer");
+GemmParams gemm_params(const void* A, long lda, long strideA, const void* W, long ldw, const void* bias, void* C, long ldc, long strideC, int M, int N, int K, int batch) {
     GemmParams p{};
     p.A = (const bf16_t*)A; p.lda = lda; p.sAb = strideA;
     p.W = (const bf16_t*)W; p.ldw = ldw;
     p.bias = (const bf16_t*)bias;
     p.C = (bf16_t*)C; p.ldc = ldc; p.sCb = strideC;
-    p.R = (const bf16_t*)R; p.ldr = ldr; p.sRb = strideR;
     p.M = M; p.N = N; p.K = K; p.batch = batch;
+    return p;
+}
+void second_problem(GemmParams& p, const void* A2, long strideA2, const void* W2, const void* bias2, void* C2, long strideC2, int M2) {
+    p.A2 = (const bf16_t*)A2; p.W2 = (const bf16_t*)W2; p.bias2 = (const bf16_t*)bias2; p.C2 = (bf16_t*)C2; p.sAb2 = strideA2; p.sCb2 = strideC2;
+    p.M2 = M2;
+}
+
+}  // namespace
+
+// Every entry point: the pointers it needs, then gemm_plan() (every shape refusal, and the launch), then alignment, then one GemmParams and launch_plan().
+
+extern "C" int tg_gemm_bf16(const void* A, long lda, long strideA, const void* W, long ldw, const void* bias,
+                            void* C, long ldc, long strideC, int M, int N, int K, int batch, int epilogue,
+                            const void* R, long ldr, long strideR, const tg_group_table* gate, hipStream_t stream) {
+    const bool gate_res = epilogue == TG_EPI_BIAS_GATE_RES, act = epilogue == TG_EPI_BIAS_KEEP_GELU || epilogue == TG_EPI_BIAS_MUL_GELU_GRAD;
+    static const char act_needs_r[] = "tg_gemm_bf16: this epilogue needs R (16-byte aligned rows)";      // one text (and TG_ERR_ARG) for a null and for a misaligned R
+    TG_REQUIRE(A && W && C, TG_ERR_ARG, "tg_gemm_bf16: null pointer");
+    TG_REQUIRE(!gate_res || (R && gate && gate->mod && gate->tok_group), TG_ERR_ARG, "tg_gemm_bf16: gate/residual epilogue needs R and a group table");
+    TG_REQUIRE(!act || R, TG_ERR_ARG, "%s", act_needs_r);
+    const GemmPlan pl = plan(GemmShape{GEMM_PLAIN, M, 0, false, N, K, batch, epilogue, 0, 0, lda, ldw});
+    TG_REQUIRE(pl.err == TG_OK, pl.err, "%s", pl.msg);
+    TG_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && ldc % 8 == 0 && strideA % 8 == 0 && strideC % 8 == 0, TG_ERR_ALIGN,
+               "tg_gemm_bf16: leading dimensions must keep 16-byte (A, W) / 8-byte (C) alignment");
+    TG_REQUIRE(tg_aligned16(A) && tg_aligned16(W) && tg_aligned16(C), TG_ERR_ALIGN, "tg_gemm_bf16: unaligned base pointer");
+    TG_REQUIRE(!gate_res || (ldr % 8 == 0 && strideR % 8 == 0 && tg_aligned16(R) && gate->mod_ld % 8 == 0 && gate->mod_batch_stride % 8 == 0 && tg_aligned16(gate->mod)),
+               TG_ERR_ALIGN, "tg_gemm_bf16: residual / gate table must be 16-byte aligned");
+    TG_REQUIRE(!act || (ldr % 8 == 0 && strideR % 8 == 0 && tg_aligned16(R)), TG_ERR_ARG, "%s", act_needs_r);
+    GemmParams p = gemm_params(A, lda, strideA, W, ldw, bias, C, ldc, strideC, M, N, K, batch);
+    p.R = (const bf16_t*)R; p.ldr = ldr; p.sRb = strideR;
+    if (gate_res) p.g = *gate;
     switch (epilogue) {
-        case TG_EPI_BIAS: return launch<TG_EPI_BIAS>(p, stream);
-        case TG_EPI_BIAS_GELU: return launch<TG_EPI_BIAS_GELU>(p, stream);
-        case TG_EPI_BIAS_SILU: return launch<TG_EPI_BIAS_SILU>(p, stream);
-        case TG_EPI_BIAS_GATE_RES:
-            TG_REQUIRE(R && gate && gate->mod && gate->tok_group, TG_ERR_ARG, "tg_gemm_bf16: gate/residual epilogue needs R and a group table");
-            TG_REQUIRE(ldr % 8 == 0 && strideR % 8 == 0 && tg_aligned16(R) && gate->mod_ld % 8 == 0 && gate->mod_batch_stride % 8 == 0 &&
-                       tg_aligned16(gate->mod), TG_ERR_ALIGN, "tg_gemm_bf16: residual / gate table must be 16-byte aligned");
-            p.g = *gate;
-            return launch<TG_EPI_BIAS_GATE_RES>(p, stream);
-        case TG_EPI_BIAS_KEEP_GELU:
-        case TG_EPI_BIAS_MUL_GELU_GRAD: {
-            TG_REQUIRE(R && ldr % 8 == 0 && strideR % 8 == 0 && tg_aligned16(R), TG_ERR_ARG, "tg_gemm_bf16: this epilogue needs R (16-byte aligned rows)");
-            TG_REQUIRE(M >= 1024 && N % BN2 == 0 && K >= 4 * BK3 && lda < (1L << 21) && ldw < (1L << 21) && tg_knob(TG_KNOB_GEMM_W4) != 0, TG_ERR_SHAPE,
-                       "tg_gemm_bf16: the keep-GELU / GELU-grad epilogues exist in the 4-wave kernel only (M >= 1024, N%%256 == 0, K >= 256)");
-            p.group_m = p.K >= 8192 ? 1 : 4;
-            const int tiles2 = ((p.M + BM2 - 1) / BM2) * (p.N / BN2) * p.batch;
-            const int n_cu = tg_device_cus();
-            if (epilogue == TG_EPI_BIAS_KEEP_GELU) {
-                TG_DYN_LDS(gemm256w4_kernel<TG_EPI_BIAS_KEEP_GELU>, W4_LDS_BYTES);
-                hipLaunchKernelGGL(gemm256w4_kernel<TG_EPI_BIAS_KEEP_GELU>, dim3(tiles2 < n_cu ? tiles2 : n_cu), dim3(256), W4_LDS_BYTES, stream, p);
-            } else {
-                TG_DYN_LDS(gemm256w4_kernel<TG_EPI_BIAS_MUL_GELU_GRAD>, W4_LDS_BYTES);
-                hipLaunchKernelGGL(gemm256w4_kernel<TG_EPI_BIAS_MUL_GELU_GRAD>, dim3(tiles2 < n_cu ? tiles2 : n_cu), dim3(256), W4_LDS_BYTES, stream, p);
-            }
-            TG_LAUNCH_CHECK("tg_gemm_bf16(256w4, activation epilogue)");
-            return TG_OK;
-        }
-        default: return tg_set_error(TG_ERR_ARG, "tg_gemm_bf16: unknown epilogue %d", epilogue);
+        case TG_EPI_BIAS: return launch_plan<TG_EPI_BIAS>(pl, p, stream);
+        case TG_EPI_BIAS_GELU: return launch_plan<TG_EPI_BIAS_GELU>(pl, p, stream);
+        case TG_EPI_BIAS_SILU: return launch_plan<TG_EPI_BIAS_SILU>(pl, p, stream);
+        case TG_EPI_BIAS_GATE_RES: return launch_plan<TG_EPI_BIAS_GATE_RES>(pl, p, stream);
+        case TG_EPI_BIAS_KEEP_GELU: return launch_plan<TG_EPI_BIAS_KEEP_GELU>(pl, p, stream);
+        default: return launch_plan<TG_EPI_BIAS_MUL_GELU_GRAD>(pl, p, stream);      // the plan has refused every other value
     }
+}
+
+extern "C" long tg_gemm_kernel(int M, int N, int K, long lda, long ldw) {
+    const GemmPlan pl = plan(GemmShape{GEMM_PLAIN, M, 0, false, N, K, 1, TG_EPI_BIAS, 0, 0, lda, ldw});
+    return pl.err == TG_OK ? (long)pl.kernel : pl.err;
 }
 
 extern "C" int tg_gemm_bf16_pair(const void* A1, long strideA1, const void* W1, const void* bias1, void* C1, long strideC1, int M1,
                                  const void* A2, long strideA2, const void* W2, const void* bias2, void* C2, long strideC2, int M2,
                                  long lda, long ldw, long ldc, int N, int K, int batch, int epilogue, hipStream_t stream) {
     TG_REQUIRE(A1 && W1 && C1 && A2 && W2 && C2, TG_ERR_ARG, "tg_gemm_bf16_pair: null pointer");
-    TG_REQUIRE(M1 >= 1024 && M2 >= 1024 && N > 0 && K > 0 && batch > 0 && N % BN2 == 0 && K % BK == 0, TG_ERR_SHAPE,
-               "tg_gemm_bf16_pair: both problems must be 256^2-kernel shapes (M >= 1024, N%%256 == 0, K%%64 == 0)");
-    TG_REQUIRE(epilogue == TG_EPI_BIAS || epilogue == TG_EPI_BIAS_GELU || epilogue == TG_EPI_BIAS_SILU, TG_ERR_ARG,
-               "tg_gemm_bf16_pair: bias / GELU / SiLU epilogues only");
+    const GemmPlan pl = plan(GemmShape{GEMM_PAIR, M1, M2, true, N, K, batch, epilogue, 0, 0, lda, ldw});
+    TG_REQUIRE(pl.err == TG_OK, pl.err, "%s", pl.msg);
     TG_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && ldc % 8 == 0 && strideA1 % 8 == 0 && strideC1 % 8 == 0 && strideA2 % 8 == 0 && strideC2 % 8 == 0 &&
                tg_aligned16(A1) && tg_aligned16(W1) && tg_aligned16(C1) && tg_aligned16(A2) && tg_aligned16(W2) && tg_aligned16(C2), TG_ERR_ALIGN,
                "tg_gemm_bf16_pair: alignment");
-    GemmParams p{};
-    p.A = (const bf16_t*)A1; p.lda = lda; p.sAb = strideA1;
-    p.W = (const bf16_t*)W1; p.ldw = ldw;
-    p.bias = (const bf16_t*)bias1;
-    p.C = (bf16_t*)C1; p.ldc = ldc; p.sCb = strideC1;
-    p.M = M1; p.N = N; p.K = K; p.batch = batch;
-    p.A2 = (const bf16_t*)A2; p.W2 = (const bf16_t*)W2; p.bias2 = (const bf16_t*)bias2; p.C2 = (bf16_t*)C2; p.sAb2 = strideA2; p.sCb2 = strideC2;
-    p.M2 = M2;
+    GemmParams p = gemm_params(A1, lda, strideA1, W1, ldw, bias1, C1, ldc, strideC1, M1, N, K, batch);
+    second_problem(p, A2, strideA2, W2, bias2, C2, strideC2, M2);
     switch (epilogue) {
-        case TG_EPI_BIAS: return launch<TG_EPI_BIAS>(p, stream);
-        case TG_EPI_BIAS_GELU: return launch<TG_EPI_BIAS_GELU>(p, stream);
-        default: return launch<TG_EPI_BIAS_SILU>(p, stream);
+        case TG_EPI_BIAS: return launch_plan<TG_EPI_BIAS>(pl, p, stream);
+        case TG_EPI_BIAS_GELU: return launch_plan<TG_EPI_BIAS_GELU>(pl, p, stream);
+        default: return launch_plan<TG_EPI_BIAS_SILU>(pl, p, stream);
     }
 }
 
@@ -1079,55 +1058,28 @@ extern "C" int tg_gemm_bf16_qkv(const void* A1, long strideA1, const void* W1, c
                                 long lda, long ldw, long ldc, int N, int K, int batch, int v_col0, hipStream_t stream) {
     TG_REQUIRE(A1 && W1 && C1 && Vt1, TG_ERR_ARG, "tg_gemm_bf16_qkv: null pointer");
     TG_REQUIRE(!A2 || (W2 && C2 && Vt2), TG_ERR_ARG, "tg_gemm_bf16_qkv: second problem needs W2, C2 and Vt2");
-    TG_REQUIRE(M1 >= 1024 && (!A2 || M2 >= 1024) && N > 0 && batch > 0 && N % BN2 == 0 && K % BK3 == 0 && K >= 4 * BK3, TG_ERR_SHAPE,
-               "tg_gemm_bf16_qkv: needs the 4-wave kernel's shapes (M >= 1024, N%%256 == 0, K%%64 == 0, K >= 256)");
-    TG_REQUIRE(v_col0 > 0 && v_col0 < N && v_col0 % BN2 == 0, TG_ERR_SHAPE, "tg_gemm_bf16_qkv: v_col0 must be a multiple of 256 inside (0, N)");
-    TG_REQUIRE(vt_ld1 % 64 == 0 && vt_ld1 >= M1 && (!A2 || (vt_ld2 % 64 == 0 && vt_ld2 >= M2)), TG_ERR_SHAPE,
-               "tg_gemm_bf16_qkv: vt_ld must be a multiple of 64 and >= M");
+    const GemmPlan pl = plan(GemmShape{GEMM_QKV, M1, M2, A2 != nullptr, N, K, batch, TG_EPI_BIAS, 0, v_col0, lda, ldw, 0, 0, vt_ld1, vt_ld2});
+    TG_REQUIRE(pl.err == TG_OK, pl.err, "%s", pl.msg);
     TG_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && ldc % 8 == 0 && strideA1 % 8 == 0 && strideC1 % 8 == 0 && strideA2 % 8 == 0 && strideC2 % 8 == 0 &&
                tg_aligned16(A1) && tg_aligned16(W1) && tg_aligned16(C1) && tg_aligned16(Vt1) && tg_aligned16(A2) && tg_aligned16(W2) &&
                tg_aligned16(C2) && tg_aligned16(Vt2), TG_ERR_ALIGN, "tg_gemm_bf16_qkv: alignment");
-    const bool w4_off = tg_knob(TG_KNOB_GEMM_W4) == 0;
-    TG_REQUIRE(lda < (1L << 21) && ldw < (1L << 21), TG_ERR_SHAPE, "tg_gemm_bf16_qkv: leading dimensions must be < 2^21 elements");
-    TG_REQUIRE(!w4_off, TG_ERR_ARG, "tg_gemm_bf16_qkv: only the 4-wave GEMM kernel has the V^T epilogue (TG_GEMM_W4=0 is set)");
-    GemmParams p{};
-    p.A = (const bf16_t*)A1; p.lda = lda; p.sAb = strideA1;
-    p.W = (const bf16_t*)W1; p.ldw = ldw;
-    p.bias = (const bf16_t*)bias1;
-    p.C = (bf16_t*)C1; p.ldc = ldc; p.sCb = strideC1;
-    p.M = M1; p.N = N; p.K = K; p.batch = batch;
+    GemmParams p = gemm_params(A1, lda, strideA1, W1, ldw, bias1, C1, ldc, strideC1, M1, N, K, batch);
     p.Vt = (bf16_t*)Vt1; p.vt_ld = vt_ld1; p.vt_col0 = v_col0;
     if (A2) {
-        p.A2 = (const bf16_t*)A2; p.W2 = (const bf16_t*)W2; p.bias2 = (const bf16_t*)bias2; p.C2 = (bf16_t*)C2; p.sAb2 = strideA2; p.sCb2 = strideC2;
-        p.M2 = M2; p.Vt2 = (bf16_t*)Vt2; p.vt_ld2 = vt_ld2;
+        second_problem(p, A2, strideA2, W2, bias2, C2, strideC2, M2);
+        p.Vt2 = (bf16_t*)Vt2; p.vt_ld2 = vt_ld2;
     }
-    return launch<TG_EPI_BIAS>(p, stream);
+    return launch_plan<TG_EPI_BIAS>(pl, p, stream);
 }
 
 extern "C" int tg_gemm_bf16_lora(const void* A, long lda, long strideA, const void* W, long ldw, const void* bias,
                                  const void* T, long ldt, long strideT, const void* B, long ldb, float scale,
                                  void* C, long ldc, long strideC, int M, int N, int K, int R, int batch, hipStream_t stream) {
     TG_REQUIRE(A && W && T && B && C, TG_ERR_ARG, "tg_gemm_bf16_lora: null pointer");
-    TG_REQUIRE(M >= 1024 && N > 0 && batch > 0 && N % BN2 == 0 && K % BK3 == 0 && K >= 4 * BK3, TG_ERR_SHAPE,
-               "tg_gemm_bf16_lora: needs the 4-wave kernel's shapes (M >= 1024, N%%256 == 0, K%%64 == 0, K >= 256): M=%d N=%d K=%d batch=%d", M, N, K, batch);
-    TG_REQUIRE(R % BK3 == 0 && R >= BK3 && R <= 6 * BK3, TG_ERR_SHAPE, "tg_gemm_bf16_lora: the rank must be a multiple of 64 in 64..384 (R=%d)", R);
-    TG_REQUIRE(lda < (1L << 21) && ldw < (1L << 21) && ldt < (1L << 21) && ldb < (1L << 21) && lda >= K && ldw >= K && ldt >= R && ldb >= R, TG_ERR_SHAPE,
-               "tg_gemm_bf16_lora: leading dimensions must cover their rows and be < 2^21 elements");
-    TG_REQUIRE(tg_knob(TG_KNOB_GEMM_W4) != 0, TG_ERR_SHAPE, "tg_gemm_bf16_lora: only the 4-wave GEMM kernel has the low-rank tail (TG_GEMM_W4=0 is set)");
+    const GemmPlan pl = plan(GemmShape{GEMM_LORA, M, 0, false, N, K, batch, TG_EPI_BIAS, R, 0, lda, ldw, ldt, ldb});
+    TG_REQUIRE(pl.err == TG_OK, pl.err, "%s", pl.msg);
     TG_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && ldt % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0 && strideA % 8 == 0 && strideT % 8 == 0 && strideC % 8 == 0 &&
                tg_aligned16(A) && tg_aligned16(W) && tg_aligned16(T) && tg_aligned16(B) && tg_aligned16(C), TG_ERR_ALIGN, "tg_gemm_bf16_lora: alignment");
-    GemmParams p{};
-    p.A = (const bf16_t*)A; p.lda = lda; p.sAb = strideA;
-    p.W = (const bf16_t*)W; p.ldw = ldw;
-    p.bias = (const bf16_t*)bias;
-    p.C = (bf16_t*)C; p.ldc = ldc; p.sCb = strideC;
-    p.M = M; p.N = N; p.K = K; p.batch = batch;
-    p.group_m = K >= 8192 ? 1 : 4;
-    LoraTail lt{(const bf16_t*)T, ldt, strideT, (const bf16_t*)B, ldb, R, scale};
-    const int tiles = ((M + BM2 - 1) / BM2) * (N / BN2) * batch;
-    const int n_cu = tg_device_cus();
-    TG_DYN_LDS((gemm256w4_kernel<TG_EPI_BIAS, LoraTail>), W4_LDS_BYTES);
-    hipLaunchKernelGGL((gemm256w4_kernel<TG_EPI_BIAS, LoraTail>), dim3(tiles < n_cu ? tiles : n_cu), dim3(256), W4_LDS_BYTES, stream, p, lt);
-    TG_LAUNCH_CHECK("tg_gemm_bf16_lora");
-    return TG_OK;
+    const LoraTail lt{(const bf16_t*)T, ldt, strideT, (const bf16_t*)B, ldb, R, scale};
+    return launch_plan<TG_EPI_BIAS>(pl, gemm_params(A, lda, strideA, W, ldw, bias, C, ldc, strideC, M, N, K, batch), stream, lt);
 }

@@ -116,15 +116,12 @@ def gemm(a, w, bias, out, epilogue=L.EPI_BIAS, residual=None, gate=None):
 def gemm_act_supported(M, N, K, lda=0, ldw=0):
     """Shapes that have the training step's activation epilogues (EPI_BIAS_KEEP_GELU: `residual` is the second OUTPUT, gelu of the kept pre-activation;
     EPI_BIAS_MUL_GELU_GRAD: `residual` is the kept pre-activation): the 4-wave GEMM kernel's.  Elsewhere: gemm(EPI_BIAS) + tg_act."""
-    return (M >= 1024 and N % 256 == 0 and K % 64 == 0 and K >= 256 and max(lda, ldw, K) < (1 << 21)      # csrc/gemm.hip: 32-bit buffer offsets in the 4-wave kernel
-            and L.debug_get("TG_GEMM_W4") != 0)                                                            # the knob the library dispatches on, not the environment
+    return L.gemm_kernel(M, N, K, lda, ldw) == 2
 
 
 def gemm_lora_supported(M, N, K, R, lda=0, ldw=0, ldt=0, ldb=0):
-    """Shapes tg_gemm_bf16_lora takes (the 4-wave GEMM kernel's, and a rank that is a multiple of 64 in 64..384).  Elsewhere: gemm(EPI_BIAS) + the
-    accumulating gemm(EPI_BIAS_GATE_RES) with a gate table that holds the scale."""
-    return (M >= 1024 and N % 256 == 0 and K % 64 == 0 and K >= 256 and R % 64 == 0 and 64 <= R <= 384 and max(lda, ldw, ldt, ldb, K) < (1 << 21)
-            and L.debug_get("TG_GEMM_W4") != 0)
+    """Shapes tg_gemm_bf16_lora takes.  Elsewhere: gemm(EPI_BIAS) + the accumulating gemm(EPI_BIAS_GATE_RES) with a gate table that holds the scale."""
+    return L.gemm_kernel(M, N, K, lda, ldw) == 2 and R % 64 == 0 and 64 <= R <= 384 and max(ldt, ldb) < (1 << 21)
 
 
 def gemm_lora(a, w, bias, t, b, scale, out):
@@ -143,9 +140,13 @@ def gemm_lora(a, w, bias, t, b, scale, out):
     return out
 
 
+def gemm_pair_supported(M1, M2, N, K):
+    return L.gemm_kernel(M1, N, K) >= 1 and L.gemm_kernel(M2, N, K) >= 1
+
+
 def gemm_pair(a1, w1, bias1, out1, a2, w2, bias2, out2, epilogue=L.EPI_BIAS):
     """out1 = epi(a1 @ w1^T + bias1) and out2 = epi(a2 @ w2^T + bias2) in one launch (tg_gemm_bf16_pair): same N, K, batch, leading
-    dimensions; [B, M, K] activations with M >= 1024."""
+    dimensions; both problems on a 256x256 kernel (gemm_pair_supported)."""
     for n, t in (("a1", a1), ("w1", w1), ("out1", out1), ("a2", a2), ("w2", w2), ("out2", out2)):
         _chk(t, n)
     B, M1, Kd, lda, sa1 = _bmk(a1)
@@ -160,7 +161,7 @@ def gemm_pair(a1, w1, bias1, out1, a2, w2, bias2, out2, epilogue=L.EPI_BIAS):
 
 def gemm_qkv_supported(M, N, K, v_col0):
     """Shapes the fused QKV + V^T launch (tg_gemm_bf16_qkv) takes; TG_GEMM_W4=0 (the cross-check tests' switch to the 8-wave GEMM) disables it too."""
-    return M >= 1024 and N % 256 == 0 and K % 64 == 0 and K >= 256 and v_col0 % 256 == 0 and L.debug_get("TG_GEMM_W4") != 0
+    return L.gemm_kernel(M, N, K) == 2 and v_col0 % 256 == 0 and 0 < v_col0 < N
 
 
 def gemm_qkv(a1, w1, bias1, out1, vt1, a2=None, w2=None, bias2=None, out2=None, vt2=None, v_col0=None):

@@ -85,8 +85,9 @@ PROTOTYPES = {
     "tg_tile_blend": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
 }
 
-# name -> argtypes of the `long tg_*_floats(...)` workspace-size queries
+# name -> argtypes of the `long tg_*(...)` pure host queries (workspace sizes, which kernel a shape gets)
 QUERIES = {
+    "tg_gemm_kernel": [C.c_int, C.c_int, C.c_int, C.c_long, C.c_long],
     "tg_groupnorm_partial_floats": [C.c_long, C.c_int],
     "tg_conv3d_gn_partial_floats": [C.c_int, C.c_int, C.c_int],
     "tg_conv3d_up2_subpixel_gn_floats": [C.c_int, C.c_int, C.c_int],
@@ -125,7 +126,7 @@ def load():
         fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
         fn.argtypes = argtypes
         fn.restype = C.c_int
-    for name, argtypes in QUERIES.items():   # workspace-size queries: pure host functions returning a count of floats
+    for name, argtypes in QUERIES.items():   # pure host functions returning a long (mostly a count of floats)
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_long
@@ -157,12 +158,10 @@ def debug_set(knob, value):
     return old.value
 
 
-def debug_get(knob):
-    """tg_debug_get: the value a dispatch knob has NOW (default, environment at load time, or a later debug_set) — what the library itself will dispatch on."""
-    lib = load()
-    v = C.c_long(0)
-    check(lib.tg_debug_get(knob.encode(), C.byref(v)), f"tg_debug_get({knob})")
-    return v.value
+def gemm_kernel(M, N, K, lda=0, ldw=0):
+    """tg_gemm_kernel: what the library launches for this shape NOW (csrc/gemm_plan.h, the TG_GEMM_W4 knob included): 0 the 128x128 tile, 1 the 8-wave 256x256
+    kernel, 2 the 4-wave one, < 0 a refused shape.  A leading dimension left at 0 means contiguous rows (K)."""
+    return load().tg_gemm_kernel(M, N, K, lda or K, ldw or K)
 
 
 def check(code, what):

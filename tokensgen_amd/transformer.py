@@ -553,7 +553,7 @@ class CogVideoXTransformer3DModel(nn.Module):
         blk = self.transformer_blocks[i]
         p = f"l{i}."
         # QKV projections (+ vip-weight projections over ALL tokens: x rows and vip rows share vip_to_*)
-        paired = use_vip and N1 >= 1024 and (3 * D) % 256 == 0       # both projections in one launch of the 256^2 kernel
+        paired = use_vip and K.gemm_pair_supported(N1, N, 3 * D, D)       # both projections in one launch of the 256^2 kernel
         # ... with V written transposed by the GEMM epilogue (no transpose_v pass; the V columns of QKV / QKVv are then never written)
         pad64 = lambda n: (n + 63) // 64 * 64
         # the vip keys' V^T can be read as the tail columns of the all-keys image only if pad64(Np) keys from column N1 stay inside a row
