@@ -3,7 +3,7 @@
 
     import tokensgen_amd.compat; tokensgen_amd.compat.install_longvgen_alias()
     from longvgen.models import CogVideoXTransformer3DModel            # -> tokensgen_amd.transformer
-    from longvgen.schedulers import CogVideoXDPMScheduler              # -> tokensgen_amd.scheduler
+    from longvgen.schedulers import CogVideoXDPMScheduler              # -> tokensgen_amd.scheduler (CogVideoXDDIMScheduler too)
     from longvgen.fifo_sampling import cogvideo_fifo_mp_v2             # -> tokensgen_amd.fifo
     from longvgen.pipeline import MPFIFOVideoIPAdapterCogVideoXPipeline, LongVGenCogVideoXPipeline
     from longvgen.video_ipadapter import Resampler                     # -> tokensgen_amd.resampler
@@ -34,7 +34,7 @@ def install_longvgen_alias(force=False):
     root.__path__ = []
     subs = {
         "models": dict(CogVideoXTransformer3DModel=transformer.CogVideoXTransformer3DModel, AutoencoderKLCogVideoX=vae.AutoencoderKLCogVideoX),
-        "schedulers": dict(CogVideoXDPMScheduler=scheduler.CogVideoXDPMScheduler),
+        "schedulers": dict(CogVideoXDPMScheduler=scheduler.CogVideoXDPMScheduler, CogVideoXDDIMScheduler=scheduler.CogVideoXDDIMScheduler),
         "fifo_sampling": dict(cogvideo_fifo_mp_v2=fifo.cogvideo_fifo_mp_v2),
         "pipeline": dict(MPFIFOVideoIPAdapterCogVideoXPipeline=pipeline.MPFIFOVideoIPAdapterCogVideoXPipeline,
                          LongVGenCogVideoXPipeline=pipeline_t2to.LongVGenCogVideoXPipeline),

@@ -94,7 +94,8 @@ class FifoWorker:
             tv = torch.as_tensor(np.asarray(t, dtype=np.int64))
             ramp = (1 - torch.cos(math.pi * ((self.num_inference_steps - tv) / self.num_inference_steps) ** 5.0)) / 2
             gpf = torch.stack([1 + self.guidance_scale * ramp, 1 + self.guidance_scale_img * ramp], dim=1).to(torch.float32).contiguous().to(self.device)
-        x_out, x0 = self.scheduler.window_step(pred.contiguous(), x[0].contiguous(), old_x0.contiguous(), noise.contiguous(),
+        # (a CogVideoXDDIMScheduler takes the same call; it ignores old_x0, noise, t_back and has_old, and the driver sends noise=None)
+        x_out, x0 = self.scheduler.window_step(pred.contiguous(), x[0].contiguous(), old_x0.contiguous(), None if noise is None else noise.contiguous(),
                                                list(map(int, t)), list(map(int, prev_t)), t_back, list(has_old),
                                                self.guidance_scale, self.guidance_scale_img, gpf)
         return x_out[None], x0
@@ -104,7 +105,7 @@ class FifoWorker:
                     image_embeddings=None, split_branches=False):
         """latents [1,nf,C,H,W] bf16; old_x0 [nf,C,H,W] (rows without an estimate are ignored via has_old);
         t/prev_t/next_t: length-nf integer sequences (next_t <= 0 means "no back step", :544);
-        noise [nf,2,C,H,W] bf16.  Returns (latents_out [1,nf,C,H,W], x0 [nf,C,H,W]).
+        noise [nf,2,C,H,W] bf16 (None under a CogVideoXDDIMScheduler).  Returns (latents_out [1,nf,C,H,W], x0 [nf,C,H,W]).
         split_branches: run the guidance branches as separate batch-1 forwards, one after the other (what the ranks of a split iteration do, on one GPU)."""
         kw = dict(latents=latents, t=t, grid_t=grid_t, cond_grid_t=cond_grid_t, image_embeddings=image_embeddings)
         pred = torch.cat([self.predict(h, **kw) for h in range(self.branches)], dim=0) if split_branches else self.predict(None, **kw)
@@ -274,6 +275,11 @@ def cogvideo_fifo_mp_v2(pipe_list, base_output, noise_seed=0, step_noise_fn=None
     if split_small_iterations and predict_fn is not None and finish_fn is not None and n_branches > 1:
         nb_split = n_branches
     noise = _SeededNoise(noise_seed, dev)
+    # DDIM (beyond the reference, whose worker asserts the DPM class, :536): the step is deterministic, so the per-window step noise is neither created nor
+    # sent; the window schedule, the exchange and the seeded tail noise are the same
+    from .scheduler import CogVideoXDDIMScheduler
+    if isinstance(getattr(pipe, "scheduler", None), CogVideoXDDIMScheduler):
+        step_noise_fn = lambda i, rank, shape: None
     step_noise_fn = step_noise_fn or noise.step
     tail_noise_fn = tail_noise_fn or noise.tail
 

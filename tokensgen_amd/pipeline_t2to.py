@@ -89,6 +89,7 @@ class LongVGenCogVideoXPipeline:
         """:566-912.  height/width/num_frames_per_chunk are the condensed-token grid (8, 12, 4 in the shipped configs).
         step_noise: optional callable (i, k) -> bf16 gaussian shaped like the latents (k = 0: first draw of step i, 1: the 2M
         branch's draw); default: `generator`, drawn in the reference's order and dtype (the sample's, scheduling_dpm:452,460).
+        With a CogVideoXDDIMScheduler nothing is drawn after the initial latents and step_noise is never called.
         cfg_parallel: see tokensgen_amd/cfg_parallel.py (default: split the two CFG halves over ranks 0/1 when >= 2 ranks run)."""
         if prompt is not None or negative_prompt is not None:
             raise NotImplementedError("T5 prompt encoding is upstream of the hot path: pass prompt_embeds and negative_prompt_embeds")
@@ -138,6 +139,8 @@ class LongVGenCogVideoXPipeline:
             return torch.randn((1,) + shape, generator=generator, device=gdev, dtype=BF16).to(dev)[0]
 
         old_x0 = None
+        from .scheduler import CogVideoXDDIMScheduler
+        ddim = isinstance(self.scheduler, CogVideoXDDIMScheduler)
         cfg_mode = CP.resolve(cfg_parallel)
         zeros = torch.zeros(shape, dtype=torch.float32, device=dev)
         noise = torch.zeros((nfr, 2) + shape[1:], dtype=BF16, device=dev)
@@ -153,6 +156,9 @@ class LongVGenCogVideoXPipeline:
             g = self._guidance_scale if do_cfg else 1.0
             prev_t = ts[i + 1] if i + 1 < len(ts) else -1
             t_back = ts[i - 1] if i > 0 else None
+            if ddim:                                         # :862 — deterministic: the f32 variant of the same fused launch on the scheduler's (t, prev_t) rows, no draw
+                latents = self.scheduler.fused_step(pred.reshape((2,) + shape), latents[0], [t] * nfr, [prev_t] * nfr, g, f32_math=True, f32_state=True)[0][None]
+                continue
             has = old_x0 is not None
             second = has and prev_t >= 0                     # the 2M branch draws a second gaussian and keeps that one (:452-463)
             n0 = draw(i, 0)

@@ -26,6 +26,7 @@ ref_shim.install()
 from longvgen.models.cogvideox_transformer_3d import CogVideoXBlock, CogVideoXTransformer3DModel  # noqa: E402
 from longvgen.models.embeddings import get_3d_rotary_pos_embed, get_3d_rotary_pos_embed_v2  # noqa: E402
 from longvgen.schedulers.scheduling_dpm_cogvideox import CogVideoXDPMScheduler  # noqa: E402
+from longvgen.schedulers.scheduling_ddim_cogvideox import CogVideoXDDIMScheduler  # noqa: E402
 import importlib.util  # noqa: E402
 
 from oracle import dit_ref as O  # noqa: E402  (only for make_state_dict: seeded weights + names)
@@ -188,6 +189,50 @@ def gen_scheduler():
     out["add_noise_to_xt"] = dict(x=x, noise=n, out=s.add_noise_to_xt(x, n, torch.Tensor([999]).long()))
     torch.save(out, os.path.join(GOLD, "scheduler.pt"))
     print("scheduler.pt", len(out["steps"]), "steps")
+
+
+SCHED_KW = dict(prediction_type="v_prediction", rescale_betas_zero_snr=True, snr_shift_scale=1.0, timestep_spacing="trailing")
+DDIM_PAIRS = [(999, 979, True), (979, 959, True), (499, 479, True), (19, -1, True), (19, -1, False)]     # (t, prev_t, set_alpha_to_one)
+
+
+@torch.no_grad()
+def gen_ddim_scheduler():
+    """The reference CogVideoXDDIMScheduler (longvgen/schedulers/scheduling_ddim_cogvideox.py): tables, timestep lists, `step` on seeded
+    [1, 3, 16, 4, 6] inputs for DDIM_PAIRS x the three prediction types (epsilon not at t = 999, where it divides by sqrt(0)) in three dtype
+    settings — all fp64; an fp32 model output (the `.float()` of a bf16 tensor, as both pipelines pass) with a bf16 sample; all bf16 — and
+    add_noise / get_velocity.  One input pair per (t, prev_t) row, shared by the prediction types and dtype settings."""
+    out = dict(tables={}, timesteps={}, inputs=[], steps=[])
+    for one in (True, False):
+        s = CogVideoXDDIMScheduler(set_alpha_to_one=one, **SCHED_KW)
+        out["tables"][one] = dict(alphas_cumprod=s.alphas_cumprod.clone(), betas=s.betas.clone(), final_alpha_cumprod=s.final_alpha_cumprod.clone())
+    for tag, n, kw in (("trailing50", 50, {}), ("trailing52", 52, {}), ("leading50_offset0", 50, dict(timestep_spacing="leading")),
+                       ("leading50_offset1", 50, dict(timestep_spacing="leading", steps_offset=1)), ("linspace7", 7, dict(timestep_spacing="linspace"))):
+        s = CogVideoXDDIMScheduler(**dict(SCHED_KW, **kw))
+        s.set_timesteps(n)
+        out["timesteps"][tag] = s.timesteps.clone()
+    g = torch.Generator().manual_seed(15)
+    shape = (1, 3, 16, 4, 6)
+    for row, (t, pt, one) in enumerate(DDIM_PAIRS):
+        mo, x = torch.randn(shape, generator=g), torch.randn(shape, generator=g)
+        out["inputs"].append(dict(t=t, prev_t=pt, set_alpha_to_one=one, model_output=mo, sample=x))
+        for ptype in ("v_prediction", "epsilon", "sample"):
+            if ptype == "epsilon" and t == 999:
+                continue
+            s = CogVideoXDDIMScheduler(set_alpha_to_one=one, **dict(SCHED_KW, prediction_type=ptype))
+            s.set_timesteps(50)
+            for tag, m_, x_ in (("f64", mo.double(), x.double()), ("f32_bf16", mo.bfloat16().float(), x.bfloat16()), ("bf16", mo.bfloat16(), x.bfloat16())):
+                prev, x0 = s.step(m_, torch.tensor(t), torch.tensor(pt), x_, return_dict=False)
+                out["steps"].append(dict(row=row, t=t, prev_t=pt, set_alpha_to_one=one, prediction_type=ptype, dtypes=tag,
+                                         prev_sample=prev.clone(), x0=x0.clone()))
+    s = CogVideoXDDIMScheduler(**SCHED_KW)
+    out["train"] = []
+    for dt in (torch.float32, torch.bfloat16):
+        a, n = torch.randn(3, 2, 4, 2, 3, generator=g).to(dt), torch.randn(3, 2, 4, 2, 3, generator=g).to(dt)
+        ts = torch.tensor([999, 500, 3])
+        out["train"].append(dict(dtype=str(dt), sample=a, noise=n, timesteps=ts, noisy=s.add_noise(a, n, ts).clone(),
+                                 velocity=s.get_velocity(a, n, ts).clone()))
+    torch.save(out, os.path.join(GOLD, "scheduler_ddim.pt"))
+    print("scheduler_ddim.pt", len(out["steps"]), "steps")
 
 
 @torch.no_grad()
@@ -402,8 +447,13 @@ def gen_resampler():
 
 
 @torch.no_grad()
-def gen_t2to():
-    """Run the reference LongVGenCogVideoXPipeline.__call__ (pipeline_cogvideox_t2to.py:566-912) on CPU with a tiny plain
+def gen_t2to(ddim=False):
+    """ddim=True -> t2to_ddim_tiny.pt: the same run under the reference's CogVideoXDDIMScheduler (no SDE draws; the fp32 case keeps the sampled
+    latents only).  pipeline_cogvideox_t2to.py:863 calls `scheduler.step(noise_pred, t, latents, ...)` — the argument order of diffusers' DDIM
+    class; the reference's own class takes prev_timestep third and raises TypeError on that call.  The scheduler used here is that class with
+    the ARGUMENTS REORDERED and nothing else: prev_t is the next entry of its own timesteps (-1 after the last), which is what :861 computes and
+    what the To2V pipeline passes (:1269-1278).
+    Run the reference LongVGenCogVideoXPipeline.__call__ (pipeline_cogvideox_t2to.py:566-912) on CPU with a tiny plain
     patch-1 DiT: 6 DPM steps, dynamic CFG, CPU generator (initial latents + every SDE draw), real PCA fitted with the
     reference's pca.PCA on seeded data.  Stored: inputs, the initial latents, every gaussian in draw order, the sampled
     latents before the tail, the final condensed tokens, and the 16 PCA rows / mean the tail actually uses."""
@@ -439,6 +489,13 @@ def gen_t2to():
         m = m.eval().to(dt)
         sched = CogVideoXDPMScheduler(prediction_type="v_prediction", rescale_betas_zero_snr=True, snr_shift_scale=1.0,
                                       timestep_spacing="trailing")
+        if ddim:
+            class _T2ToArgumentOrder(CogVideoXDDIMScheduler):
+                def step(self, model_output, timestep, sample, return_dict=True):
+                    ts_ = self.timesteps.tolist()
+                    i_ = ts_.index(int(timestep))
+                    return super().step(model_output, timestep, ts_[i_ + 1] if i_ + 1 < len(ts_) else -1, sample, return_dict=return_dict)
+            sched = _T2ToArgumentOrder(**SCHED_KW)
         g = torch.Generator().manual_seed(801)
         prompt = torch.randn(1, 8, TINY["text_embed_dim"], generator=g).to(dt)
         negative = torch.randn(1, 8, TINY["text_embed_dim"], generator=g).to(dt)
@@ -476,14 +533,25 @@ def gen_t2to():
         if dt == torch.float32:
             common = dict(mean=mean, std=std, pca_mean=pca.mean_.clone(), pca_components16=pca.components_[:16].clone(),
                           sd_checksum=sd_checksum(sd))
+    if ddim:
+        assert all(len(c["step_draws"]) == 0 for c in results.values())
+        for c in results.values():
+            del c["step_draws"]
+        del results[str(torch.float32)]["frames"]
+        torch.save(dict(cfg=cfg, weight_seed=800, input_seed=801, gen_seed=802, H=H, W=W, nfc=nfc, chunks=chunks, steps=steps,
+                        guidance_scale=6.0, scheduler="CogVideoXDDIMScheduler", **common, cases=results), os.path.join(GOLD, "t2to_ddim_tiny.pt"))
+        print("t2to_ddim_tiny.pt", tuple(results[str(torch.bfloat16)]["frames"].shape))
+        return
     torch.save(dict(cfg=cfg, weight_seed=800, input_seed=801, gen_seed=802, H=H, W=W, nfc=nfc, chunks=chunks, steps=steps,
                     guidance_scale=6.0, **common, cases=results), os.path.join(GOLD, "t2to_tiny.pt"))
     print("t2to_tiny.pt", tuple(results[str(torch.float32)]["frames"].shape), len(results[str(torch.float32)]["step_draws"]), "draws")
 
 
 @torch.no_grad()
-def gen_base_stage(variant=False):
-    """variant=True -> base_stage_dyn_sep.pt: the same run with use_dynamic_cfg + use_separate_guidance (guidance_scale_img 4.0, 16 steps) — the
+def gen_base_stage(variant=False, ddim=False):
+    """ddim=True -> base_stage_ddim_tiny.pt: the default run (static guidance 6.0) under the reference's CogVideoXDDIMScheduler, 50 trailing steps:
+    the pipeline's non-DPM branch (:1270-1278); the only gaussian is the initial latents.
+    variant=True -> base_stage_dyn_sep.pt: the same run with use_dynamic_cfg + use_separate_guidance (guidance_scale_img 4.0, 16 steps) — the
     branch in which the reference re-assigns its LOCAL `guidance_scale_img = 1 + guidance_scale_img * ramp` on every step (:1257), so the image
     weight compounds from step to step and the compounded value is what the stage exports to the FIFO driver (:1336).  The Resampler stub returns
     a fixed seeded tensor there (the "tokens of an all-zero video" of the third CFG branch), zeros in the default fixture.
@@ -495,7 +563,7 @@ def gen_base_stage(variant=False):
     fifo_latents, fifo_old_pred_original_sample, orig_latents, the position grids and the RoPE table the pipeline built."""
     import contextlib
     ref = load_ref_module("longvgen/pipeline/pipeline_cogvideox_mp_fifo.py", "ref_pipe_mp_fifo")
-    H, W, nf, T, chunks = 4, 6, 13, (16 if variant else 52), 2
+    H, W, nf, T, chunks = 4, 6, 13, (50 if ddim else 16 if variant else 52), 2
     unc_tok = torch.randn(1, 4, 128, 2, 3, generator=torch.Generator().manual_seed(903)) if variant else torch.zeros(1, 4, 128, 2, 3)
     rq = types.SimpleNamespace(num_temporal_queries=4, num_height_queries=2, num_width_queries=3, max_temporal_seq_len=13, max_height_seq_len=2,
                                max_width_seq_len=3)
@@ -537,7 +605,7 @@ def gen_base_stage(variant=False):
     for dt in (torch.float32, torch.bfloat16):
         m, sd = tiny_model(900)
         m = m.to(dt)
-        sched = make_sched()
+        sched = CogVideoXDDIMScheduler(**SCHED_KW) if ddim else make_sched()
         g = torch.Generator().manual_seed(901)
         prompt = torch.randn(1, 8, TINY["text_embed_dim"], generator=g).to(dt)
         negative = torch.randn(1, 8, TINY["text_embed_dim"], generator=g).to(dt)
@@ -571,7 +639,10 @@ def gen_base_stage(variant=False):
                           vip_image_rotary_grid=[np.asarray(a).copy() for a in out.vip_image_rotary_grid],
                           vip_condition_rotary_grid=[np.asarray(a).copy() for a in out.vip_condition_rotary_grid],
                           vip_nf_per_chunk=out.vip_nf_per_chunk, sd_checksum=sd_checksum(sd))
-    name = "base_stage_dyn_sep.pt" if variant else "base_stage_tiny.pt"
+    name = "base_stage_ddim_tiny.pt" if ddim else "base_stage_dyn_sep.pt" if variant else "base_stage_tiny.pt"
+    if ddim:
+        assert all(len(c["step_draws"]) == 0 for c in cases.values())
+        common["scheduler"] = "CogVideoXDDIMScheduler"
     torch.save(dict(weight_seed=900, input_seed=901, gen_seed=902, H=H, W=W, chunks=chunks, steps=T, guidance_scale=6.0, vip_scale=[0.6],
                     **(dict(guidance_scale_img=4.0, use_dynamic_cfg=True, use_separate_guidance=True, unc_tok=unc_tok) if variant else {}),
                     **common, cases=cases), os.path.join(GOLD, name))
@@ -758,7 +829,8 @@ if __name__ == "__main__":
     ap.add_argument("--only", default=None)
     a = ap.parse_args()
     os.makedirs(GOLD, exist_ok=True)
-    jobs = dict(dit=gen_dit_tiny, vip=gen_vip_processor, sched=gen_scheduler, fifo=gen_fifo, vae=gen_vae, resampler=gen_resampler, t2to=gen_t2to, base=gen_base_stage, base_dyn_sep=lambda: gen_base_stage(variant=True), vae_geom=gen_vae_geometry, vae_t26=gen_vae_t26, train=gen_train, fifo_worker=gen_fifo_worker)
+    jobs = dict(dit=gen_dit_tiny, vip=gen_vip_processor, sched=gen_scheduler, fifo=gen_fifo, vae=gen_vae, resampler=gen_resampler, t2to=gen_t2to, base=gen_base_stage, base_dyn_sep=lambda: gen_base_stage(variant=True), vae_geom=gen_vae_geometry, vae_t26=gen_vae_t26, train=gen_train, fifo_worker=gen_fifo_worker,
+                ddim_sched=gen_ddim_scheduler, ddim_base=lambda: gen_base_stage(ddim=True), ddim_t2to=lambda: gen_t2to(ddim=True))
     if a.only:
         jobs = {a.only: jobs.get(a.only, gen_full_block)}
     for k, fn in jobs.items():
