@@ -307,6 +307,24 @@ int tg_pca_inverse(const void* lat, const float* std16, const float* mean16, con
 int tg_pca_project16(const void* x, long ldx, int rows, int D, const float* comp, const float* pmean, const float* mean16,
                      const float* std16, int hw, void* out, hipStream_t stream);
 
+/* Fitting the T2To token statistics (what pca.pt / mean.pt / std.pt hold): pca.py:40-58 `fit` / `transform`, consumed by train_cogvideo_t2to.py:1761-1773
+ * `pca_normalization`.  Two streaming passes over bf16 token rows x [rows][D] (row stride ldx elements; rows ordered as the caller likes); the totals are
+ * fp64 running sums owned by the caller, every call adds to them.  D % 128 == 0, 128 <= D <= 4096, rows >= 1, ldx >= D, x and ldx 16-byte aligned; rows past
+ * `rows` and the columns D .. ldx-1 are never read.  Both are deterministic (one owner per output or partials added in a fixed order, no atomics).
+ *
+ * tg_gram_accumulate:  gram[i][j] += sum_r x[r][i] x[r][j]   (fp64 [D][D], the FULL matrix, gram[i][j] and gram[j][i] bitwise equal: only the upper
+ *                      128 x 128 tiles are computed, the mirror is a copy)      colsum[i] += sum_r x[r][i]   (fp64 [D])
+ *   bf16 x bf16 products on the MFMA with fp32 accumulation; at most tg_gram_fold_rows() (256) rows are summed in fp32 before the partial joins the fp64 total.
+ * tg_pca_coef_stats:   y_j = sum_c (x[r][c] - pmean[c]) * comp[j][c] per row in fp32 (tg_pca_project16 before its normalisation), j < ncoef, then
+ *                      sum[j] += sum_r y_j, sumsq[j] += sum_r y_j^2 (fp64 [ncoef]), and extreme[j] (fp32 [ncoef], started at 0 by the caller) becomes the y_j of
+ *                      largest magnitude seen so far, signed, replaced only when |new| > |old|: the row that decides the component's sign in pca.py:30-32.
+ *   comp fp32 [ncoef][D] (16-byte aligned), ncoef % 16 == 0, 16 <= ncoef <= 64; ws: tg_pca_coef_stats_ws_floats(rows, ncoef) floats, 8-byte aligned. */
+long tg_gram_fold_rows(void);
+int tg_gram_accumulate(const void* x, long ldx, long rows, int D, double* gram, double* colsum, hipStream_t stream);
+long tg_pca_coef_stats_ws_floats(long rows, int ncoef);
+int tg_pca_coef_stats(const void* x, long ldx, long rows, int D, const float* comp, int ncoef, const float* pmean, double* sum, double* sumsq,
+                      float* extreme, float* ws, hipStream_t stream);
+
 
 /* Training forward of one attention call: tg_attention_fwd with a single key segment that ALSO writes, per query row, the log-sum-exp of the
  * scaled scores in the log2 domain (lse fp32 [batch][heads][nq]): what flash-attention keeps for its backward

@@ -70,6 +70,8 @@ PROTOTYPES = {
     "tg_pca_inverse": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "tg_pca_lowrank_filter": [_vp, _l, _vp, _vp, _vp, _l, _i, _i, _i, _vp],
     "tg_pca_project16": [_vp, _l, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp],
+    "tg_gram_accumulate": [_vp, _l, _l, _i, _vp, _vp, _vp],
+    "tg_pca_coef_stats": [_vp, _l, _l, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "tg_conv3d_cl": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _l, _i, _i, _i, _vp, _vp, _vp, _vp],
     "tg_conv3d_up2_subpixel": [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _l, _i, _vp, _vp, _vp],
     "tg_groupnorm_finalize": [_vp, _l, _i, _f, _vp, _vp],
@@ -104,6 +106,8 @@ QUERIES = {
     "tg_vpred_loss_partial_floats": [C.c_int, C.c_long],
     "tg_grad_norm_ws_floats": [],
     "tg_lora_wgrad_ws_floats": [C.c_int, C.c_int, C.c_int],
+    "tg_gram_fold_rows": [],
+    "tg_pca_coef_stats_ws_floats": [C.c_long, C.c_int],
 }
 
 TG_BWD_ONE_KERNEL = 1
