@@ -535,6 +535,27 @@ int tg_adamw8bit_step(void* param, float* grad, uint8_t* state1, uint8_t* state2
                       const float* qmap1, const float* qmap2, const tg_adamw8bit_row* rows, int nrows, long nblocks, int block_size, int step,
                       float lr, float beta1, float beta2, float eps, float weight_decay, const float* clip_coef, int zero_grad, hipStream_t stream);
 
+/* Prodigy (the yaml's `optimizer: prodigy`; train_cogvideo_to2v.py:1109-1132, train_cogvideo_t2to.py get_optimizer; the algorithm is prodigyopt 1.0
+ * Prodigy.step restated: DESIGN §8) over a whole arena: ONE step = three launches on `stream`, no host synchronisation.
+ *   per element: exp_avg / exp_avg_sq / s / delta fp32, p0 bf16 (the start values); the parameter is never updated in place: delta = x - x0 is kept
+ *     exactly in fp32 and param = bf16_rne(p0 + delta) is rewritten every step (an in-place bf16 update loses the first updates and d never grows).
+ *   state: TG_PRODIGY_STATE_DOUBLES fp64 on the device: [0] d, [1] d_max, [2] d_numerator, [3] d_hat and [4] d_denom of the last step, [5] dlr =
+ *     d * lr * bias correction with the d BEFORE the last step (what its update used), [6] 1.0 if the last step was skipped (d_denom == 0: every
+ *     gradient so far was zero; nothing but this flag is stored), else 0.0, [7] reserved.  Initialise to {d0, d0, 0, 0, 0, 0, 0, 0}.
+ *   pass 1 (all elements, gradient of elements below clip_n scaled by *clip_coef, device pointer, NULL = 1): the EMA updates of exp_avg, exp_avg_sq
+ *     and s with coefficients computed from the device's d, zero_grad, and per workgroup one fp64 pair (sum g * (x0 - x), sum |s|) into ws
+ *     (tg_prodigy_ws_doubles() doubles) — lanes accumulate in fp64, combined in a fixed order, no atomics: bitwise reproducible.
+ *   finalize (one thread): sums the pairs in index order, applies the d_hat / d / d_max rules in fp64.
+ *   pass 2: delta -= dlr * exp_avg / (sqrt(exp_avg_sq) + d * eps) (+ decoupled weight decay), param = bf16_rne(p0 + delta).
+ * n and clip_n must be multiples of 64 (every arena is); every arena, state and ws 16-byte aligned.  eps > 0 keeps the arena's zero
+ * padding zero (0 / (0 + d * eps)).  growth_rate may be +inf. */
+#define TG_PRODIGY_STATE_DOUBLES 8
+long tg_prodigy_ws_doubles(void);
+int tg_prodigy_step(void* param, float* grad, float* exp_avg, float* exp_avg_sq, float* s, float* delta, const void* p0, double* state, double* ws,
+                    long n, long clip_n, int step, double lr, double beta1, double beta2, double beta3, double eps, double weight_decay, double d0,
+                    double d_coef, double growth_rate, int decouple, int use_bias_correction, int safeguard_warmup, const float* clip_coef,
+                    int zero_grad, hipStream_t stream);
+
 /* Training loss of the To2V step and its gradient w.r.t. the model output (train_cogvideo_to2v.py:1995-2004; get_velocity
  * scheduling_dpm_cogvideox.py:521-538), per frame f (per-frame timesteps) over frame_elems elements:
  *   pred = bf16(bf16(sa_f * noisy) - bf16(sb_f * out))    sa_f = sqrt(acp_t), sb_f = sqrt(1 - acp_t), both cast to bf16 like the reference

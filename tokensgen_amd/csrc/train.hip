@@ -690,6 +690,113 @@ __global__ __launch_bounds__(OPT_BLOCK) void adamw_kernel(bf16_t* __restrict__ p
     }
 }
 
+// Prodigy (header: tg_prodigy_step).  Everything that depends on d is computed on the device from the fp64 state buffer, so a step never waits for the host.
+enum { PD_D = 0, PD_DMAX = 1, PD_NUM = 2, PD_DHAT = 3, PD_DEN = 4, PD_DLR = 5, PD_SKIP = 6 };
+struct ProdigyHyper {
+    double lr, bc, beta1, beta2, beta3, eps, wd, d0, d_coef, growth;
+    int safeguard;
+};
+typedef __attribute__((ext_vector_type(4))) float pd_f4;
+typedef __attribute__((ext_vector_type(4))) unsigned short pd_h4;
+
+// a + b summed over the wave in a fixed (butterfly) order: every lane ends with the same bits, every run with the same bits
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// Pass 1: the three EMAs and the two sums of the d estimate.  Four elements per lane and iteration (16-byte fp32 accesses, 8 bytes of p0); n4 = n / 4 and
+// clip4 = clip_n / 4 are whole numbers of vectors (n, clip_n multiples of 64).  WD_GRAD: weight decay added to the gradient (not decoupled) — the only case in
+// which this pass needs x itself, hence p0.  g is read and zeroed through one pointer (as adamw_kernel).
+template <bool WD_GRAD>
+__global__ __launch_bounds__(OPT_BLOCK) void prodigy_stats_kernel(float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, float* __restrict__ s,
+                                                                  const float* __restrict__ delta, const bf16_t* __restrict__ p0, long n4, long clip4,
+                                                                  const float* __restrict__ clip, const double* __restrict__ state, double* __restrict__ ws,
+                                                                  ProdigyHyper h, int zero_grad) {
+#pragma clang fp contract(off)      // every product and sum rounds as written: where b1 * m and a1 * g cancel, a fused form differs by many ulps of the result
+    const double d = state[PD_D];
+    const double dlr = d * h.lr * h.bc;
+    const float a1 = (float)(d * (1.0 - h.beta1)), a2 = (float)(d * d * (1.0 - h.beta2)), a3 = (float)((d / h.d0) * (h.safeguard ? d : dlr));
+    const float b1 = (float)h.beta1, b2 = (float)h.beta2, b3 = (float)h.beta3, wd = (float)h.wd;
+    const float cs = clip ? *clip : 1.f;
+    double num = 0.0, den = 0.0;
+    for (long i = (long)blockIdx.x * OPT_BLOCK + threadIdx.x; i < n4; i += (long)gridDim.x * OPT_BLOCK) {
+        const pd_f4 gv = reinterpret_cast<const pd_f4*>(g)[i], dv = reinterpret_cast<const pd_f4*>(delta)[i];
+        pd_f4 mv = reinterpret_cast<const pd_f4*>(m)[i], vv = reinterpret_cast<const pd_f4*>(v)[i], sv = reinterpret_cast<const pd_f4*>(s)[i];
+        pd_h4 ph = {0, 0, 0, 0};
+        if (WD_GRAD) ph = reinterpret_cast<const pd_h4*>(p0)[i];
+        const float c = i < clip4 ? cs : 1.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float gi = c * gv[k];
+            if (WD_GRAD) gi += wd * (bf16_to_f32(ph[k]) + dv[k]);
+            num += (double)gi * (double)(-dv[k]);
+            mv[k] = b1 * mv[k] + a1 * gi;
+            vv[k] = b2 * vv[k] + a2 * gi * gi;
+            sv[k] = b3 * sv[k] + a3 * gi;
+            den += (double)fabsf(sv[k]);
+        }
+        reinterpret_cast<pd_f4*>(m)[i] = mv;
+        reinterpret_cast<pd_f4*>(v)[i] = vv;
+        reinterpret_cast<pd_f4*>(s)[i] = sv;
+        if (zero_grad) reinterpret_cast<pd_f4*>(g)[i] = pd_f4{0.f, 0.f, 0.f, 0.f};
+    }
+    num = wave_sum_f64(num);
+    den = wave_sum_f64(den);
+    __shared__ double red[2 * (OPT_BLOCK / 64)];
+    if ((threadIdx.x & 63) == 0) { red[2 * (threadIdx.x >> 6)] = num; red[2 * (threadIdx.x >> 6) + 1] = den; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        ws[2 * (long)blockIdx.x] = ((red[0] + red[2]) + red[4]) + red[6];
+        ws[2 * (long)blockIdx.x + 1] = ((red[1] + red[3]) + red[5]) + red[7];
+    }
+}
+
+// Finalize: the partial pairs in index order, then prodigyopt's scalar rules, all fp64, one thread.
+__global__ void prodigy_finalize_kernel(const double* __restrict__ ws, int n_partial, double* __restrict__ state, ProdigyHyper h) {
+#pragma clang fp contract(off)
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double sum = 0.0, den = 0.0;
+    for (int i = 0; i < n_partial; ++i) { sum += ws[2 * i]; den += ws[2 * i + 1]; }
+    if (den == 0.0) { state[PD_SKIP] = 1.0; return; }       // every gradient so far was zero: the EMAs are still zero, pass 2 returns at once
+    double d = state[PD_D], d_max = state[PD_DMAX];
+    const double dlr = d * h.lr * h.bc;
+    const double num = h.beta3 * state[PD_NUM] + (d / h.d0) * dlr * sum;
+    const double d_hat = h.d_coef * num / den;
+    if (d == h.d0) d = fmax(d, d_hat);
+    d_max = fmax(d_max, d_hat);
+    d = fmin(d_max, d * h.growth);
+    state[PD_D] = d; state[PD_DMAX] = d_max; state[PD_NUM] = num; state[PD_DHAT] = d_hat; state[PD_DEN] = den; state[PD_DLR] = dlr; state[PD_SKIP] = 0.0;
+}
+
+// Pass 2: the Adam-shaped update of the exact displacement with the d of THIS step in the denominator and the dlr of the d before it, then the parameter.
+// WD_DEC: decoupled weight decay (on x = p0 + delta as it was before the update).
+template <bool WD_DEC>
+__global__ __launch_bounds__(OPT_BLOCK) void prodigy_update_kernel(bf16_t* __restrict__ p, const float* __restrict__ m, const float* __restrict__ v,
+                                                                   float* __restrict__ delta, const bf16_t* __restrict__ p0, long n4,
+                                                                   const double* __restrict__ state, double eps, double wd) {
+#pragma clang fp contract(off)
+    if (state[PD_SKIP] != 0.0) return;
+    const float dlr = (float)state[PD_DLR], deps = (float)(state[PD_D] * eps), wdl = (float)(wd * state[PD_DLR]);
+    for (long i = (long)blockIdx.x * OPT_BLOCK + threadIdx.x; i < n4; i += (long)gridDim.x * OPT_BLOCK) {
+        const pd_f4 mv = reinterpret_cast<const pd_f4*>(m)[i], vv = reinterpret_cast<const pd_f4*>(v)[i];
+        pd_f4 dv = reinterpret_cast<const pd_f4*>(delta)[i];
+        const pd_h4 ph = reinterpret_cast<const pd_h4*>(p0)[i];
+        pd_h4 po;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float x0 = bf16_to_f32(ph[k]);
+            float upd = dlr * (mv[k] / (sqrtf(vv[k]) + deps));
+            if (WD_DEC) upd += wdl * (x0 + dv[k]);
+            dv[k] -= upd;
+            po[k] = f32_to_bf16(x0 + dv[k]);
+        }
+        reinterpret_cast<pd_f4*>(delta)[i] = dv;
+        reinterpret_cast<pd_h4*>(p)[i] = po;
+    }
+}
+
 // Block-wise 8-bit AdamW (header: tg_adamw8bit_step).  One 256-lane workgroup per quantisation block of OPT_BLOCK * EPL elements, EPL contiguous
 // elements per lane (16-byte bf16 / 2 x 16-byte fp32 / 8-byte code accesses at EPL = 8).  The workgroup finds its tensor by a binary search over the
 // table's first_block (the same index in every lane: scalar loads).  A lane whose chunk starts inside the tensor reads its whole chunk: the chunk ends
@@ -877,6 +984,43 @@ extern "C" int tg_adamw_step(void* param, float* grad, float* exp_avg, float* ex
     hipLaunchKernelGGL(adamw_kernel, dim3(opt_blocks(n)), dim3(OPT_BLOCK), 0, stream, (bf16_t*)param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps,
                        weight_decay, bc1, bc2s, clip_coef, zero_grad);
     TG_LAUNCH_CHECK("tg_adamw_step");
+    return TG_OK;
+}
+
+extern "C" long tg_prodigy_ws_doubles(void) { return 2L * OPT_MAX_BLOCKS; }
+
+extern "C" int tg_prodigy_step(void* param, float* grad, float* exp_avg, float* exp_avg_sq, float* s, float* delta, const void* p0, double* state, double* ws,
+                               long n, long clip_n, int step, double lr, double beta1, double beta2, double beta3, double eps, double weight_decay, double d0,
+                               double d_coef, double growth_rate, int decouple, int use_bias_correction, int safeguard_warmup, const float* clip_coef,
+                               int zero_grad, hipStream_t stream) {
+    TG_REQUIRE(param && grad && exp_avg && exp_avg_sq && s && delta && p0 && state && ws, TG_ERR_ARG, "tg_prodigy_step: null pointer");
+    TG_REQUIRE(n > 0 && step >= 1, TG_ERR_SHAPE, "tg_prodigy_step: n and step must be positive");
+    TG_REQUIRE(clip_n >= 0 && clip_n <= n, TG_ERR_SHAPE, "tg_prodigy_step: clip_n %ld outside [0, %ld]", clip_n, n);
+    TG_REQUIRE(n % 64 == 0 && clip_n % 64 == 0, TG_ERR_SHAPE, "tg_prodigy_step: n %ld and clip_n %ld must be multiples of 64 (arena slots)", n, clip_n);
+    TG_REQUIRE(lr > 0.0 && eps > 0.0 && d0 > 0.0, TG_ERR_SHAPE, "tg_prodigy_step: lr, eps and d0 must be positive (a step at lr 0 is the caller's no-op)");
+    TG_REQUIRE(tg_aligned16(grad) && tg_aligned16(exp_avg) && tg_aligned16(exp_avg_sq) && tg_aligned16(s) && tg_aligned16(delta) && tg_aligned16(param) &&
+               tg_aligned16(p0) && tg_aligned16(state) && tg_aligned16(ws), TG_ERR_ALIGN, "tg_prodigy_step: arenas must be 16-byte aligned");
+    ProdigyHyper h;
+    h.lr = lr; h.beta1 = beta1; h.beta2 = beta2; h.beta3 = beta3; h.eps = eps; h.wd = weight_decay; h.d0 = d0; h.d_coef = d_coef; h.growth = growth_rate;
+    h.bc = use_bias_correction ? sqrt(1.0 - pow(beta2, (double)step)) / (1.0 - pow(beta1, (double)step)) : 1.0;
+    h.safeguard = safeguard_warmup ? 1 : 0;
+    const long n4 = n / 4, clip4 = clip_n / 4;
+    const unsigned nb = opt_blocks(n4);
+    const bool wd_grad = weight_decay != 0.0 && !decouple, wd_dec = weight_decay != 0.0 && decouple;
+    if (wd_grad)
+        hipLaunchKernelGGL(prodigy_stats_kernel<true>, dim3(nb), dim3(OPT_BLOCK), 0, stream, grad, exp_avg, exp_avg_sq, s, (const float*)delta, (const bf16_t*)p0, n4,
+                           clip4, clip_coef, (const double*)state, ws, h, zero_grad);
+    else
+        hipLaunchKernelGGL(prodigy_stats_kernel<false>, dim3(nb), dim3(OPT_BLOCK), 0, stream, grad, exp_avg, exp_avg_sq, s, (const float*)delta, (const bf16_t*)p0, n4,
+                           clip4, clip_coef, (const double*)state, ws, h, zero_grad);
+    hipLaunchKernelGGL(prodigy_finalize_kernel, dim3(1), dim3(64), 0, stream, (const double*)ws, (int)nb, state, h);
+    if (wd_dec)
+        hipLaunchKernelGGL(prodigy_update_kernel<true>, dim3(nb), dim3(OPT_BLOCK), 0, stream, (bf16_t*)param, (const float*)exp_avg, (const float*)exp_avg_sq, delta,
+                           (const bf16_t*)p0, n4, (const double*)state, eps, weight_decay);
+    else
+        hipLaunchKernelGGL(prodigy_update_kernel<false>, dim3(nb), dim3(OPT_BLOCK), 0, stream, (bf16_t*)param, (const float*)exp_avg, (const float*)exp_avg_sq, delta,
+                           (const bf16_t*)p0, n4, (const double*)state, eps, weight_decay);
+    TG_LAUNCH_CHECK("tg_prodigy_step");
     return TG_OK;
 }
 

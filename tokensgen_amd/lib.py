@@ -18,7 +18,7 @@ class GroupTable(C.Structure):
                 ("gate_col", C.c_int32 * TG_MAX_GROUPS)]
 
 
-_vp, _l, _i, _f = C.c_void_p, C.c_long, C.c_int, C.c_float
+_vp, _l, _i, _f, _d = C.c_void_p, C.c_long, C.c_int, C.c_float, C.c_double
 # name -> argtypes, exactly the prototypes of include/tokensgen_hip.h
 PROTOTYPES = {
     "tg_gemm_bf16": [_vp, _l, _l, _vp, _l, _vp, _vp, _l, _l, _i, _i, _i, _i, _i, _vp, _l, _l, C.POINTER(GroupTable), _vp],
@@ -56,6 +56,7 @@ PROTOTYPES = {
     "tg_grad_clip_coef": [_vp, _l, _f, _vp, _vp, _vp],
     "tg_adamw_step": [_vp, _vp, _vp, _vp, _l, _i, _f, _f, _f, _f, _f, _vp, _i, _vp],
     "tg_adamw8bit_step": [_vp] * 11 + [_i, _l, _i, _i, _f, _f, _f, _f, _f, _vp, _i, _vp],
+    "tg_prodigy_step": [_vp] * 9 + [_l, _l, _i] + [_d] * 9 + [_i, _i, _i, _vp, _i, _vp],
     "tg_lora_wgrad": [_vp, _l, _l, _vp, _l, _l, _i, _i, _i, _i, _vp, _l, _l, _f, _f, _vp, _vp],
     "tg_lora_merge": [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _f, _vp],
     "tg_vpred_loss_grad": [_vp, _vp, _vp, _vp, _i, _l, _f, _vp, _vp, _vp],
@@ -105,6 +106,7 @@ QUERIES = {
     "tg_colsum_partial_floats": [C.c_int, C.c_int],
     "tg_vpred_loss_partial_floats": [C.c_int, C.c_long],
     "tg_grad_norm_ws_floats": [],
+    "tg_prodigy_ws_doubles": [],
     "tg_lora_wgrad_ws_floats": [C.c_int, C.c_int, C.c_int],
     "tg_gram_fold_rows": [],
     "tg_pca_coef_stats_ws_floats": [C.c_long, C.c_int],
@@ -201,6 +203,7 @@ class Adamw8bitRow(C.Structure):
 
 
 ADAMW8BIT_FP32, ADAMW8BIT_BLOCKWISE = 0, 1
+PRODIGY_STATE_DOUBLES = 8          # TG_PRODIGY_STATE_DOUBLES: d, d_max, d_numerator, d_hat, d_denom, dlr, skipped, reserved
 
 
 class AttnSegment(C.Structure):

@@ -5,8 +5,9 @@ MI355X-first layout: every trainable parameter lives in ONE flat bf16 arena (the
 flat fp32 arena for the accumulated gradient and the optimizer state beside it.  The optimizer step is then three streaming launches over the arena
 (sum of squares -> clip coefficient on the device -> AdamW + zero_grad), and the data-parallel gradient exchange is a handful of large RCCL
 all-reduces over slices of the same buffer (xGMI rings are per-link bound: few big buckets, once per `gradient_accumulation_steps` micro-steps —
-the reference's `no_sync` for the other eight).  Two optimizers: `AdamW` keeps fp32 moments (torch.optim.AdamW); `AdamW8bit` is the yaml's
-`use_8bit_adam: true` (bitsandbytes AdamW8bit): block-wise 8-bit moments, 2 B per parameter instead of 8, on an arena built with `moments=False`.
+the reference's `no_sync` for the other eight).  Three optimizers: `AdamW` keeps fp32 moments (torch.optim.AdamW); `AdamW8bit` is the yaml's
+`use_8bit_adam: true` (bitsandbytes AdamW8bit): block-wise 8-bit moments, 2 B per parameter instead of 8, on an arena built with `moments=False`;
+`Prodigy` is the yaml's `optimizer: prodigy` (prodigyopt), learning-rate free, with two arena-wide reductions per step and its scalars on the device.
 `get_optimizer` picks one from the yaml's keys."""
 import warnings
 
@@ -322,11 +323,121 @@ class AdamW8bit:
                              "(the table's clipped flags are fixed at construction)")
 
 
+class Prodigy:
+    """prodigyopt.Prodigy (1.0; the yaml's `optimizer: prodigy`, train_cogvideo_to2v.py:1109-1132) on a ParamArena built with moments=True, with the
+    same surface as AdamW (step / coef / t / state_dict / load_state_dict) and the same clipping split.  Learning-rate free: the step size is d * lr
+    with d an estimate of the distance to the solution grown from d0 by sum g . (x0 - x) / sum |s|; lr stays near 1.  The arena's exp_avg /
+    exp_avg_sq are Prodigy's (scaled by d and d^2); this optimizer adds s (fp32), delta = x - x0 (fp32) and p0 = x0 (bf16), 10 B per parameter, and
+    writes param = bf16(p0 + delta) every step: an update applied to the bf16 parameter in place is rounded away while d is still d0, x0 - x stays
+    0 and d never grows.  d, d_max, the numerator and the last step's d_hat / denominator / dlr live on the device in fp64
+    (`scalars`, layout: include/tokensgen_hip.h); a step is three launches and never synchronises — `stats()` is the one call that does."""
+
+    KIND = "prodigy"
+    _STATE = ("s", "delta", "p0", "scalars")
+    _SCALARS = ("d", "d_max", "d_numerator", "d_hat", "d_denom", "dlr")
+
+    def __init__(self, arena, lr=1.0, betas=(0.9, 0.999), beta3=None, eps=1e-8, weight_decay=0.0, decouple=True, use_bias_correction=False,
+                 safeguard_warmup=False, d0=1e-6, d_coef=1.0, growth_rate=float("inf"), max_grad_norm=1.0, clip_elems=None):
+        if arena.exp_avg is None:
+            raise NotImplementedError("optimizer 'prodigy' (Prodigy) needs the arena's fp32 moments (exp_avg / exp_avg_sq): build the ParamArena with "
+                                      "moments=True; an arena built with moments=False is for AdamW8bit")
+        if not (eps > 0 and d0 > 0):
+            raise ValueError(f"Prodigy: eps {eps} and d0 {d0} must be positive")
+        self.arena, self.lr, self.betas, self.eps, self.wd, self.max_norm = arena, lr, tuple(betas), eps, weight_decay, max_grad_norm
+        self.beta3 = float(self.betas[1]) ** 0.5 if beta3 is None else float(beta3)
+        self.decouple, self.use_bias_correction, self.safeguard_warmup = bool(decouple), bool(use_bias_correction), bool(safeguard_warmup)
+        self.d0, self.d_coef, self.growth_rate = float(d0), float(d_coef), float(growth_rate)
+        self.clip_elems = arena.numel if clip_elems is None else int(clip_elems)
+        self.t = 0
+        dev = arena.param.device
+        self.p0 = arena.param.clone()
+        self.delta = torch.zeros(arena.numel, dtype=torch.float32, device=dev)
+        self.s = torch.zeros(arena.numel, dtype=torch.float32, device=dev)
+        self.scalars = torch.tensor([self.d0, self.d0] + [0.0] * (L.PRODIGY_STATE_DOUBLES - 2), dtype=torch.float64, device=dev)
+        lib = L.load()
+        self._ws = torch.empty(lib.tg_grad_norm_ws_floats(), dtype=torch.float32, device=dev)
+        self._ws64 = torch.empty(lib.tg_prodigy_ws_doubles(), dtype=torch.float64, device=dev)
+        self.coef = torch.ones(2, dtype=torch.float32, device=dev)        # [total norm, clip coefficient] of the last step (device side)
+
+    @torch.no_grad()
+    def step(self, lr=None, zero_grad=True):
+        a, lib = self.arena, L.load()
+        self.t += 1
+        lr = self.lr if lr is None else lr
+        if not lr > 0:                                                     # prodigyopt: no statistics at lr 0, the denominator is 0, nothing moves
+            if zero_grad:
+                a.grad.zero_()
+            return
+        st = K._stream()
+        clip_ptr = None
+        nc = self.clip_elems
+        if self.max_norm is not None and self.max_norm > 0 and nc > 0:
+            L.check(lib.tg_grad_clip_coef(a.grad.data_ptr(), nc, float(self.max_norm), self._ws.data_ptr(), self.coef.data_ptr(), st), "tg_grad_clip_coef")
+            clip_ptr = self.coef.data_ptr() + 4
+        L.check(lib.tg_prodigy_step(a.param.data_ptr(), a.grad.data_ptr(), a.exp_avg.data_ptr(), a.exp_avg_sq.data_ptr(), self.s.data_ptr(),
+                                    self.delta.data_ptr(), self.p0.data_ptr(), self.scalars.data_ptr(), self._ws64.data_ptr(), a.numel,
+                                    nc if clip_ptr is not None else 0, self.t, float(lr), float(self.betas[0]), float(self.betas[1]), self.beta3,
+                                    float(self.eps), float(self.wd), self.d0, self.d_coef, self.growth_rate, int(self.decouple),
+                                    int(self.use_bias_correction), int(self.safeguard_warmup), clip_ptr, 1 if zero_grad else 0, st), "tg_prodigy_step")
+
+    def stats(self):
+        """{"d", "d_max", "d_numerator", "d_hat", "d_denom", "dlr"} as Python floats (d_hat, d_denom, dlr: of the last step that was not skipped).
+        Synchronises with the device; d * lr is the effective learning rate a Prodigy run logs."""
+        return dict(zip(self._SCALARS, self.scalars.cpu().tolist()))
+
+    # ---- checkpoint / resume: AdamW's dict + "s" / "delta" / "p0" (flat arenas), "scalars" (the fp64 state buffer) and, in "hyper", kind and
+    # Prodigy's own knobs.  The parameters are saved separately (as for AdamW); a resume must put back exactly bf16(p0 + delta).
+    def _hyper(self):
+        return {"lr": self.lr, "betas": tuple(self.betas), "beta3": self.beta3, "eps": self.eps, "weight_decay": self.wd, "max_grad_norm": self.max_norm,
+                "clip_elems": self.clip_elems, "kind": self.KIND, "decouple": self.decouple, "use_bias_correction": self.use_bias_correction,
+                "safeguard_warmup": self.safeguard_warmup, "d0": self.d0, "d_coef": self.d_coef, "growth_rate": self.growth_rate}
+
+    def state_dict(self):
+        a = self.arena
+        sd = {"t": int(self.t), "exp_avg": a.exp_avg.detach().cpu().clone(), "exp_avg_sq": a.exp_avg_sq.detach().cpu().clone(),
+              "grad": a.grad.detach().cpu().clone(), "layout": a.layout(), "hyper": self._hyper()}
+        for name in self._STATE:
+            sd[name] = getattr(self, name).detach().cpu().clone()
+        return sd
+
+    @torch.no_grad()
+    def load_state_dict(self, sd, chunk=1 << 26):
+        a = self.arena
+        h = sd.get("hyper", {})
+        kind = h.get("kind", "adamw")
+        if kind != self.KIND:
+            raise ValueError(f"Prodigy.load_state_dict: the checkpoint holds {kind!r} optimizer state, not {self.KIND!r}")
+        if [(n, int(o), tuple(sh)) for n, o, sh in sd["layout"]] != a.layout():
+            raise ValueError("Prodigy.load_state_dict: the checkpoint's arena layout (names / offsets / shapes) differs from this arena's")
+        dst = {"exp_avg": a.exp_avg, "exp_avg_sq": a.exp_avg_sq, "grad": a.grad, **{name: getattr(self, name) for name in self._STATE}}
+        for name, d in dst.items():
+            t = sd[name]
+            if t.numel() != d.numel() or t.dtype != d.dtype:
+                raise ValueError(f"Prodigy.load_state_dict: {name} has {t.numel()} {t.dtype} elements, this optimizer has {d.numel()} {d.dtype}")
+        for lo in range(0, a.numel, chunk):                                # the parameters must be the checkpoint's own bf16(p0 + delta), bit for bit
+            sl = slice(lo, min(a.numel, lo + chunk))
+            want = (sd["p0"][sl].to(a.param.device).float() + sd["delta"][sl].to(a.param.device)).to(BF16)
+            if not torch.equal(want.view(torch.int16), a.param[sl].view(torch.int16)):
+                raise ValueError("Prodigy.load_state_dict: the arena's param is not bitwise bf16(p0 + delta) of the checkpoint — load the parameters "
+                                 "saved with this checkpoint before the optimizer state")
+        for name, d in dst.items():
+            d.copy_(sd[name].to(d.device))
+        self.t = int(sd["t"])
+        self.lr, self.betas, self.eps = h.get("lr", self.lr), tuple(h.get("betas", self.betas)), h.get("eps", self.eps)
+        self.beta3, self.wd, self.max_norm = float(h.get("beta3", self.beta3)), h.get("weight_decay", self.wd), h.get("max_grad_norm", self.max_norm)
+        self.clip_elems = int(h.get("clip_elems", self.clip_elems))
+        self.decouple, self.use_bias_correction = bool(h.get("decouple", self.decouple)), bool(h.get("use_bias_correction", self.use_bias_correction))
+        self.safeguard_warmup = bool(h.get("safeguard_warmup", self.safeguard_warmup))
+        self.d0, self.d_coef, self.growth_rate = float(h.get("d0", self.d0)), float(h.get("d_coef", self.d_coef)), float(h.get("growth_rate", self.growth_rate))
+
+
 def get_optimizer(arena, cfg, clip_elems=None):
-    """The reference's get_optimizer (train_cogvideo_to2v.py:1056-1130) for its yaml keys: optimizer, use_8bit_adam, learning_rate, adam_beta1 /
-    adam_beta2, adam_epsilon, adam_weight_decay, max_grad_norm (argparse defaults where a key is missing).  `cfg`: a dict or an object with those
-    attributes.  "adamw" -> AdamW, "adamw" + use_8bit_adam -> AdamW8bit (build the arena with moments=False); use_8bit_adam with another optimizer is
-    ignored with a warning, an unknown optimizer falls back to "adamw" with a warning; "adam" and "prodigy" raise NotImplementedError."""
+    """The reference's get_optimizer (train_cogvideo_to2v.py:1056-1133) for its yaml keys: optimizer, use_8bit_adam, learning_rate, adam_beta1 /
+    adam_beta2, adam_epsilon, adam_weight_decay, max_grad_norm, prodigy_beta3 / prodigy_decouple / prodigy_use_bias_correction /
+    prodigy_safeguard_warmup (argparse defaults where a key is missing).  `cfg`: a dict or an object with those attributes.  "adamw" -> AdamW,
+    "adamw" + use_8bit_adam -> AdamW8bit (build the arena with moments=False), "prodigy" -> Prodigy (arena with moments=True; warns when
+    learning_rate <= 0.1, as the reference does); use_8bit_adam with another optimizer is ignored with a warning, an unknown optimizer falls back to
+    "adamw" with a warning; "adam" raises NotImplementedError."""
     get = cfg.get if isinstance(cfg, dict) else (lambda k, d=None: getattr(cfg, k, d))
     name = str(get("optimizer", "adam")).lower()
     if name not in ("adam", "adamw", "prodigy"):
@@ -340,8 +451,14 @@ def get_optimizer(arena, cfg, clip_elems=None):
         raise NotImplementedError("optimizer 'adam' (torch.optim.Adam / bitsandbytes Adam8bit: weight decay added to the gradient) is not implemented; "
                                   "the training yamls use 'adamw'")
     if name == "prodigy":
-        raise NotImplementedError("optimizer 'prodigy' (prodigyopt.Prodigy: learning-rate-free D-adaptation) is not implemented; the training yamls "
-                                  "use 'adamw'")
+        lr = float(get("learning_rate", 1e-4))
+        if lr <= 0.1:
+            warnings.warn("Learning rate is too low. When using prodigy, it's generally better to set learning rate around 1.0")
+        beta3 = get("prodigy_beta3", None)
+        return Prodigy(arena, lr=lr, betas=(float(get("adam_beta1", 0.9)), float(get("adam_beta2", 0.95))), beta3=None if beta3 is None else float(beta3),
+                       weight_decay=float(get("adam_weight_decay", 1e-4)), eps=float(get("adam_epsilon", 1e-8)),
+                       decouple=bool(get("prodigy_decouple", False)), use_bias_correction=bool(get("prodigy_use_bias_correction", False)),
+                       safeguard_warmup=bool(get("prodigy_safeguard_warmup", False)), max_grad_norm=float(get("max_grad_norm", 1.0)), clip_elems=clip_elems)
     kw = dict(lr=float(get("learning_rate", 1e-4)), betas=(float(get("adam_beta1", 0.9)), float(get("adam_beta2", 0.95))),
               eps=float(get("adam_epsilon", 1e-8)), weight_decay=float(get("adam_weight_decay", 1e-4)), max_grad_norm=float(get("max_grad_norm", 1.0)),
               clip_elems=clip_elems)

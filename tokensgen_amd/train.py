@@ -872,7 +872,7 @@ class To2VTrainStep:
         self.latent_frames_per_chunk = int(rp.get("max_temporal_seq_len", 13))
 
     # ---- checkpoint / resume of the loop state (the reference: accelerator.save_state / load_state, train_cogvideo_to2v.py:1690-1716): the
-    # optimizer's dict (optim.AdamW / AdamW8bit .state_dict: step count, moments, the gradient arena) + the position inside the accumulation window
+    # optimizer's dict (optim.AdamW / AdamW8bit / Prodigy .state_dict: step count, moments, the gradient arena) + the position inside the accumulation window
     def state_dict(self):
         return {"optimizer": self.opt.state_dict(), "micro": int(self.micro)}
 

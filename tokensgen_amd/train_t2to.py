@@ -736,7 +736,7 @@ def _linear_grads(grads, name, x2d, dy2d, want):
 
 
 def make_arena(trainer, cfg):
-    """ParamArena of the trainer's trainable set in t2to_arena_order (fp32 moments only for plain AdamW; AdamW8bit keeps its own state), the
+    """ParamArena of the trainer's trainable set in t2to_arena_order (fp32 moments for plain AdamW and for Prodigy; AdamW8bit keeps its own state), the
     trainer moved onto it, and the optimizer of the yaml's keys (optim.get_optimizer).  Returns (arena, optimizer)."""
     get = cfg.get if isinstance(cfg, dict) else (lambda k, d=None: getattr(cfg, k, d))
     eight_bit = bool(get("use_8bit_adam", False)) and str(get("optimizer", "adam")).lower() in ("adam", "adamw")

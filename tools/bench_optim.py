@@ -1,9 +1,11 @@
 """Optimizer step at the full To2V trainable layout (42 layers of vip_ tensors + the Resampler, 1.97 B parameters): optim.AdamW (fp32 moments) against
-optim.AdamW8bit (block-wise 8-bit moments) in the same process, alternating, timed with device events.  Each step = clip coefficient (one read of
-the clipped gradient) + the AdamW launch; algorithmic bytes of the AdamW pass: 28 B / element fp32 (bf16 parameter read + write, fp32 gradient
-read + zero, both fp32 moments read + written), 16 B / element 8-bit (the moments as 1-byte codes).  Also the optimizer-state memory of both,
-measured as torch.cuda.memory_allocated deltas.  Prints one JSON line; `--out PATH` also writes it to a file (the committed record is
-profiles/r7_optim_step.json)."""
+optim.AdamW8bit (block-wise 8-bit moments) and optim.Prodigy in the same process, alternating, timed with device events.  Each step = clip
+coefficient (one read of the clipped gradient) + the optimizer's launches; algorithmic bytes of the AdamW pass: 28 B / element fp32 (bf16 parameter
+read + write, fp32 gradient read + zero, both fp32 moments read + written), 16 B / element 8-bit (the moments as 1-byte codes); Prodigy 56 B /
+element: pass 1 36 (g, m, v, s, delta read; m, v, s written, g zeroed), pass 2 20 (m, v, delta, p0 read; delta, param written).  Also the
+optimizer-state memory of each, measured as torch.cuda.memory_allocated deltas.  After the timed steps Prodigy's delta must be non-zero inside the
+LAST tensor of the arena (the 64-bit element indexing, which no small test reaches).  Prints one JSON line; `--out PATH` also writes it to a file (the
+committed records are profiles/r7_optim_step.json and profiles/prodigy_step.json)."""
 import argparse
 import json
 import os
@@ -41,6 +43,7 @@ def main():
     m1 = torch.cuda.memory_allocated()
     a8 = optim.ParamArena(params, order, dev, moments=False)
     m2 = torch.cuda.memory_allocated()
+    ap = optim.ParamArena(params, order, dev)
     del model, params
     torch.cuda.empty_cache()
     n_clip = a32.prefix_elems(lambda n: not n.startswith("resampler."))
@@ -50,6 +53,9 @@ def main():
     opt8 = optim.AdamW8bit(a8, **hyper)
     torch.cuda.synchronize()
     m4 = torch.cuda.memory_allocated()
+    optp = optim.Prodigy(ap, lr=1.0, betas=(0.9, 0.95), eps=1e-8, weight_decay=1e-4, decouple=True, max_grad_norm=1.0, clip_elems=n_clip)
+    torch.cuda.synchronize()
+    m5 = torch.cuda.memory_allocated()
     state32 = (m1 - m0) - (m2 - m1)                 # the two fp32 moment arenas: what moments=False leaves out
     state8 = m4 - m3
     gen = torch.Generator(device=dev).manual_seed(3)
@@ -57,7 +63,7 @@ def main():
     for n in a32.names:
         v = a32.grad_view(n)
         grad[a32.offsets[n]:a32.offsets[n] + v.numel()].normal_(generator=gen).mul_(1e-5)
-    runs = {"adamw_fp32": (a32, opt32, 28), "adamw_8bit": (a8, opt8, 16)}
+    runs = {"adamw_fp32": (a32, opt32, 28), "adamw_8bit": (a8, opt8, 16), "prodigy": (ap, optp, 56)}
     ms = {k: [] for k in runs}
     for r in range(a.rounds + 1):                    # round 0: warm-up (code objects, first touch)
         for name, (arena, opt, _) in runs.items():
@@ -70,7 +76,7 @@ def main():
             torch.cuda.synchronize()
             if r:
                 ms[name].append(e0.elapsed_time(e1))
-    rec = {"what": "optimizer step at the full To2V trainable layout (clip coefficient + AdamW pass), device events, alternating",
+    rec = {"what": "optimizer step at the full To2V trainable layout (clip coefficient + the optimizer's pass(es)), device events, alternating",
            "params": n_params, "arena_elems": a32.numel, "rounds": a.rounds}
     for name, (arena, opt, bpe) in runs.items():
         best = min(ms[name])
@@ -79,6 +85,14 @@ def main():
                      "gbs": round(byt / best / 1e6, 1), "frac_of_8TBs": round(byt / best / 1e-3 / HBM, 3)}
     rec["state_bytes"] = {"adamw_fp32_moments": state32, "adamw_8bit": state8, "saved": state32 - state8,
                           "adamw_8bit_per_param": round(state8 / n_params, 4)}
+    last = ap.names[-1]
+    lo = ap.offsets[last]
+    moved = int(optp.delta[lo:lo + ap.views[last].numel()].count_nonzero())
+    assert moved > 0, f"Prodigy: delta is all zero inside the last tensor {last} at elements {lo}.. of {ap.numel}"
+    rec["prodigy"].update({"state_bytes_per_param": round((m5 - m4) / n_params, 4), "arena_moment_bytes_per_param": round(state32 / n_params, 4),
+                           "tbs": round(rec["prodigy"]["gbs"] / 1e3, 3), "tbs_vs_adamw_fp32": round(rec["prodigy"]["gbs"] / rec["adamw_fp32"]["gbs"], 3),
+                           "ms_vs_adamw_fp32": round(rec["prodigy"]["ms_min"] / rec["adamw_fp32"]["ms_min"], 3),
+                           "last_tensor": last, "last_tensor_offset": lo, "last_tensor_delta_nonzero": moved, "stats": optp.stats()})
     rec["speedup_8bit"] = round(rec["adamw_fp32"]["ms_min"] / rec["adamw_8bit"]["ms_min"], 3)
     line = json.dumps(rec)
     print(line)
