@@ -687,6 +687,21 @@ int tg_cl_to_ncdhw(const void* src, long ld, int C, int T, int H, int W, void* d
 int tg_tile_blend(const void* a, void* b, int is_fp32, int C, int T, int Ha, int Wa, int Hb, int Wb, int axis, int extent,
                   hipStream_t stream);
 
+/* The pixel ends of a run (csrc/video.hip; host side: tokensgen_amd/video_io.py).
+ * tg_video_resample: src uint8 [F][H][W][3] (a decoder's layout) -> dst bf16 [F][3][oh][ow] in [-1, 1]: `video / 255.` -> antialiased separable resize -> centre crop
+ * or zero pad -> `* 2 - 1` of longvgen/data/long_video.py:61-76 with resize_for_rectangle_crop / ResolutionControl of longvgen/data/utils.py:13-140, the resize taken as
+ * F.interpolate(align_corners=False, antialias=True).  The filter comes as tables: output row i reads source rows y0[i] .. y0[i] + ny[i] - 1 with weights wy[i][0 .. ny[i])
+ * (row stride taps_y floats), columns likewise; a source index outside the image contributes 0 (so y0 / x0 may be negative: the pad), the crop is a slice of the tables.
+ * Pixel = float(u8) / 255.0f, fp32 accumulation in tap order in both passes, dst = bf16_rne(2 acc - 1), no clamp.  Bitwise independent of F.  taps > 64: TG_ERR_SHAPE.
+ * tg_video_to_uint8: src bf16, element strides (stride_b, stride_c, stride_t) over contiguous H x W planes of 3 channels -> r = clamp(bf16_rne(v * 0.5f + 0.5f), 0, 1)
+ * (VaeImageProcessor.denormalize of diffusers 0.31 in the tensor's dtype; restated, source absent) as
+ *   dst_kind 0: uint8 [B][T][H][W][3] = r * 255 truncated (rounding 0: export_to_video) or rounded half to even (rounding 1: numpy_to_pil); NaN -> 0
+ *   dst_kind 1: fp32  [B][T][H][W][3] = r        dst_kind 2: bf16 [B][T][3][H][W] = r        (the "np" / "pt" outputs; a NaN stays a NaN) */
+int tg_video_resample(const void* src, int F, int H, int W, void* dst, int oh, int ow, const int32_t* y0, const int32_t* ny, const float* wy, int taps_y,
+                      const int32_t* x0, const int32_t* nx, const float* wx, int taps_x, hipStream_t stream);
+int tg_video_to_uint8(const void* src, long stride_b, long stride_c, long stride_t, int B, int T, int H, int W, void* dst, int dst_kind, int rounding,
+                      hipStream_t stream);
+
 /* Dispatch overrides for the cross-check tests — NOT part of the operator surface.  The library reads no environment variable and keeps no other
  * process-wide state: the defaults are the shipped path, and these knobs only choose between two PRODUCT kernels of the same operator (each pair is held
  * bitwise or to rounding against each other by tests/).  Knobs: TG_ATTN_PP_MIN_WG (1024: workgroups from which the 8-wave attention kernel is used),

@@ -869,3 +869,44 @@ def tile_blend(a, b, axis, extent):
         return b
     L.check(L.load().tg_tile_blend(_p(a), _p(b), 1 if a.dtype == torch.float32 else 0, C, T, Ha, Wa, Hb, Wb, axis, extent, _stream()), "tg_tile_blend")
     return b
+
+
+def video_resample(frames_u8, tables, oh, ow):
+    """tg_video_resample: uint8 [F, H, W, 3] contiguous -> bf16 [F, 3, oh, ow] in [-1, 1].  tables = (y0, ny, wy, x0, nx, wx) on the same device: int32 [oh], int32
+    [oh], fp32 [oh, taps_y] and the same per output column (tokensgen_amd.video_io.resample_plan builds them)."""
+    _chk(frames_u8, "frames", torch.uint8)
+    if frames_u8.dim() != 4 or frames_u8.shape[-1] != 3 or not frames_u8.is_contiguous():
+        raise ValueError(f"frames: expected contiguous [F, H, W, 3], got {tuple(frames_u8.shape)}")
+    y0, ny, wy, x0, nx, wx = tables
+    for t, name, dt, n in ((y0, "y0", torch.int32, oh), (ny, "ny", torch.int32, oh), (wy, "wy", torch.float32, oh), (x0, "x0", torch.int32, ow),
+                           (nx, "nx", torch.int32, ow), (wx, "wx", torch.float32, ow)):
+        _chk(t, name, dt)
+        if t.device != frames_u8.device or not t.is_contiguous() or t.shape[0] != n or t.dim() != (2 if dt == torch.float32 else 1):
+            raise ValueError(f"{name}: expected a contiguous table of {n} rows on {frames_u8.device}, got {tuple(t.shape)} on {t.device}")
+    F, H, W, _ = frames_u8.shape
+    out = torch.empty(F, 3, oh, ow, dtype=BF16, device=frames_u8.device)
+    L.check(_launch("video_resample", L.load().tg_video_resample, _p(frames_u8), F, H, W, _p(out), oh, ow, _p(y0), _p(ny), _p(wy), wy.shape[1], _p(x0), _p(nx),
+                    _p(wx), wx.shape[1], _stream()), "tg_video_resample")
+    return out
+
+
+VIDEO_U8, VIDEO_F32, VIDEO_BF16_PLANAR = 0, 1, 2
+
+
+def video_to_uint8(video, channel_dim, kind=VIDEO_U8, rounding=0):
+    """tg_video_to_uint8: bf16 [B, 3, T, H, W] (channel_dim 1) or [B, T, 3, H, W] (channel_dim 2), any batch / channel / frame strides over contiguous H x W planes ->
+    uint8 [B, T, H, W, 3] (kind VIDEO_U8; rounding 0 truncates, 1 rounds half to even), fp32 [B, T, H, W, 3] in [0, 1] (VIDEO_F32) or bf16 [B, T, 3, H, W] in [0, 1]
+    (VIDEO_BF16_PLANAR)."""
+    _chk(video, "video")
+    if video.dim() != 5 or channel_dim not in (1, 2) or video.shape[channel_dim] != 3:
+        raise ValueError(f"video: expected [B, 3, T, H, W] or [B, T, 3, H, W] with the channel axis named, got {tuple(video.shape)} / channel_dim={channel_dim}")
+    B, H, W = video.shape[0], video.shape[3], video.shape[4]
+    t_dim = 3 - channel_dim
+    T = video.shape[t_dim]
+    if H * W > 1 and (video.stride(4) != 1 or (H > 1 and video.stride(3) != W)):
+        raise ValueError("video: the H x W planes must be contiguous")
+    shape, dt = {VIDEO_U8: ((B, T, H, W, 3), torch.uint8), VIDEO_F32: ((B, T, H, W, 3), torch.float32), VIDEO_BF16_PLANAR: ((B, T, 3, H, W), BF16)}[kind]
+    out = torch.empty(shape, dtype=dt, device=video.device)
+    L.check(_launch("video_to_uint8", L.load().tg_video_to_uint8, _p(video), video.stride(0), video.stride(channel_dim), video.stride(t_dim), B, T, H, W, _p(out),
+                    kind, int(rounding), _stream()), "tg_video_to_uint8")
+    return out

@@ -73,6 +73,8 @@ PROTOTYPES = {
     "tg_pca_project16": [_vp, _l, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp],
     "tg_gram_accumulate": [_vp, _l, _l, _i, _vp, _vp, _vp],
     "tg_pca_coef_stats": [_vp, _l, _l, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    "tg_video_resample": [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp],
+    "tg_video_to_uint8": [_vp, _l, _l, _l, _i, _i, _i, _i, _vp, _i, _i, _vp],
     "tg_conv3d_cl": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _l, _i, _i, _i, _vp, _vp, _vp, _vp],
     "tg_conv3d_up2_subpixel": [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _l, _i, _vp, _vp, _vp],
     "tg_groupnorm_finalize": [_vp, _l, _i, _f, _vp, _vp],
