@@ -702,6 +702,23 @@ int tg_video_resample(const void* src, int F, int H, int W, void* dst, int oh, i
 int tg_video_to_uint8(const void* src, long stride_b, long stride_c, long stride_t, int B, int T, int H, int W, void* dst, int dst_kind, int rounding,
                       hipStream_t stream);
 
+/* How close two videos are (csrc/metrics.hip; host side: tokensgen_amd/metrics.py): calculate_psnr_pt, calculate_ssim_pt and _ssim_pth of
+ * longvgen/metrics/psnr_ssim.py:50-79, 159-195, 266-296 with rgb2ycbcr_pt(y_only=True) of longvgen/utils/color_util.py:186-208, for every image plane of two inputs at once.
+ * tg_image_metrics: out[p] = {sse, ssim_sum} (float64 [planes][2]) for plane p = (outer * n_inner + inner) * C + channel (y_only: p = outer * n_inner + inner, C == 3):
+ *   sse = sum (a - b)^2 over the h x w plane, ssim_sum = sum of the SSIM map over its (h - 10) x (w - 10) window positions; all arithmetic float64 on the 0..255 scale:
+ *   dtype 0 uint8 as it is, 1 fp32 and 2 bf16 in [0, 1] times 255.0.  Window: 11 taps, w[i] = exp(-(i - 5)^2 / (2 * 1.5^2)) normalised in float64 (tg_image_metrics_window
+ *   writes the 11 taps), separable, "valid".  Map: ((2 mu1 mu2 + c1) / (mu1^2 + mu2^2 + c1)) * ((2 s12 + c2) / (s1 + s2 + c2)), c1 = (0.01 * 255)^2, c2 = (0.03 * 255)^2.
+ *   y_only: the three channels become Y = (65.481 r + 128.553 g + 24.966 b) / 255 + 16 in float64 before anything else (the reference forms it in the input's dtype).
+ *   Pixel (outer, inner, channel, y, x) of input a is element a[outer * a_so + inner * a_si + channel * a_sc + y * a_sr + x * a_sp]: interleaved [.., H, W, 3] has
+ *   sp = 3, sc = 1; a crop is a base offset with a smaller h, w.  Strides >= 0, h, w >= 11, C in {1, 3}.  ws: tg_image_metrics_ws_doubles(planes, h, w) doubles (one pair
+ *   per tile of tg_image_metrics_tile(0) x tg_image_metrics_tile(1) window positions), ws and out 8-byte aligned.  Two launches on `stream` (tiles, then the sum of a
+ *   plane's tiles in tile order), no atomics: a plane's result does not depend on the number of planes or on its place among them. */
+long tg_image_metrics_tile(int axis);
+long tg_image_metrics_ws_doubles(long planes, int h, int w);
+int tg_image_metrics_window(double* taps);
+int tg_image_metrics(const void* a, long a_so, long a_si, long a_sc, long a_sr, long a_sp, const void* b, long b_so, long b_si, long b_sc, long b_sr, long b_sp,
+                     int dtype, int n_outer, int n_inner, int C, int h, int w, int y_only, double* ws, double* out, hipStream_t stream);
+
 /* Dispatch overrides for the cross-check tests — NOT part of the operator surface.  The library reads no environment variable and keeps no other
  * process-wide state: the defaults are the shipped path, and these knobs only choose between two PRODUCT kernels of the same operator (each pair is held
  * bitwise or to rounding against each other by tests/).  Knobs: TG_ATTN_PP_MIN_WG (1024: workgroups from which the 8-wave attention kernel is used),

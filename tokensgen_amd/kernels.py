@@ -910,3 +910,63 @@ def video_to_uint8(video, channel_dim, kind=VIDEO_U8, rounding=0):
     L.check(_launch("video_to_uint8", L.load().tg_video_to_uint8, _p(video), video.stride(0), video.stride(channel_dim), video.stride(t_dim), B, T, H, W, _p(out),
                     kind, int(rounding), _stream()), "tg_video_to_uint8")
     return out
+
+
+IMAGE_LAYOUTS = ("hwc", "chw", "bcthw", "bfchw")
+_IMAGE_DTYPES = {torch.uint8: 0, torch.float32: 1, BF16: 2}
+IMAGE_WINDOW = 11
+
+
+def _image_strides(t, layout):
+    """(n_outer, n_inner, C, H, W) and the element strides (outer, inner, channel, row, pixel) of an image batch in one of IMAGE_LAYOUTS"""
+    s = t.stride()
+    if layout == "hwc" and t.dim() == 4:            # [F, H, W, C]
+        return (1, t.shape[0], t.shape[3], t.shape[1], t.shape[2]), (0, s[0], s[3], s[1], s[2])
+    if layout == "hwc" and t.dim() == 5:            # [B, T, H, W, C]
+        return (t.shape[0], t.shape[1], t.shape[4], t.shape[2], t.shape[3]), (s[0], s[1], s[4], s[2], s[3])
+    if layout == "chw" and t.dim() == 4:            # [n, C, H, W]
+        return (1, t.shape[0], t.shape[1], t.shape[2], t.shape[3]), (0, s[0], s[1], s[2], s[3])
+    if layout == "bcthw" and t.dim() == 5:          # [B, C, T, H, W]
+        return (t.shape[0], t.shape[2], t.shape[1], t.shape[3], t.shape[4]), (s[0], s[2], s[1], s[3], s[4])
+    if layout == "bfchw" and t.dim() == 5:          # [B, F, C, H, W]
+        return (t.shape[0], t.shape[1], t.shape[2], t.shape[3], t.shape[4]), (s[0], s[1], s[2], s[3], s[4])
+    raise ValueError(f"layout {layout!r} does not describe a tensor of shape {tuple(t.shape)} (hwc: [F, H, W, C] / [B, T, H, W, C]; chw: [n, C, H, W]; bcthw; bfchw)")
+
+
+def image_metrics(a, b, layout, crop_border=0, y_only=False):
+    """tg_image_metrics: per image plane of two equally shaped uint8 (0..255), fp32 or bf16 (in [0, 1]) image batches, float64 [n_outer, n_inner, planes, 2] =
+    (sum of squared differences on the 0..255 scale over the plane, sum of the SSIM map over its (h - 10) x (w - 10) window positions), h x w the plane without
+    `crop_border` pixels on every side; planes = C, or 1 with y_only (C == 3: BT.601 luma).  layout names the axes (IMAGE_LAYOUTS); a and b may be any views with
+    non-negative strides, the crop costs no copy.  One call for all planes; a plane's numbers do not depend on the other planes of the call."""
+    for t, name in ((a, "a"), (b, "b")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: expected a tensor")
+        if t.dtype not in _IMAGE_DTYPES:
+            raise TypeError(f"{name}: expected uint8, float32 or bfloat16, got {t.dtype}")
+    if a.dtype != b.dtype:
+        raise TypeError(f"a and b must have one dtype, got {a.dtype} and {b.dtype}")
+    if layout not in IMAGE_LAYOUTS:
+        raise ValueError(f"layout must be one of {sorted(IMAGE_LAYOUTS)}, got {layout!r}")
+    if a.shape != b.shape:
+        raise ValueError(f"image shapes are different: {tuple(a.shape)}, {tuple(b.shape)}")
+    (n_outer, n_inner, Cn, H, W), sa = _image_strides(a, layout)
+    _, sb = _image_strides(b, layout)
+    if Cn not in (1, 3) or (y_only and Cn != 3):
+        raise ValueError(f"expected 1 or 3 channels (3 with y_only), got {Cn}")
+    cb = int(crop_border)
+    h, w = H - 2 * cb, W - 2 * cb
+    if cb < 0 or h < IMAGE_WINDOW or w < IMAGE_WINDOW:
+        raise ValueError(f"a {H} x {W} plane with crop_border {cb} is smaller than the {IMAGE_WINDOW} x {IMAGE_WINDOW} window")
+    if n_outer * n_inner < 1:
+        raise ValueError("no images")
+    if not (a.is_cuda and b.is_cuda) or a.device != b.device:
+        raise RuntimeError("image_metrics: expected two tensors on one GPU (tokensgen_amd has no CPU fallback)")
+    lib = L.load()
+    planes = n_outer * n_inner * (1 if y_only else Cn)
+    ws = torch.empty(lib.tg_image_metrics_ws_doubles(planes, h, w), dtype=torch.float64, device=a.device)
+    out = torch.empty(n_outer, n_inner, planes // (n_outer * n_inner), 2, dtype=torch.float64, device=a.device)
+    pa = a.data_ptr() + cb * (sa[3] + sa[4]) * a.element_size()
+    pb = b.data_ptr() + cb * (sb[3] + sb[4]) * b.element_size()
+    L.check(_launch("image_metrics", lib.tg_image_metrics, pa, *sa, pb, *sb, _IMAGE_DTYPES[a.dtype], n_outer, n_inner, Cn, h, w, int(bool(y_only)), _p(ws), _p(out),
+                    _stream()), "tg_image_metrics")
+    return out

@@ -75,6 +75,8 @@ PROTOTYPES = {
     "tg_pca_coef_stats": [_vp, _l, _l, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "tg_video_resample": [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp],
     "tg_video_to_uint8": [_vp, _l, _l, _l, _i, _i, _i, _i, _vp, _i, _i, _vp],
+    "tg_image_metrics_window": [_vp],
+    "tg_image_metrics": [_vp, _l, _l, _l, _l, _l, _vp, _l, _l, _l, _l, _l, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp],
     "tg_conv3d_cl": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _l, _i, _i, _i, _vp, _vp, _vp, _vp],
     "tg_conv3d_up2_subpixel": [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _l, _i, _vp, _vp, _vp],
     "tg_groupnorm_finalize": [_vp, _l, _i, _f, _vp, _vp],
@@ -112,6 +114,8 @@ QUERIES = {
     "tg_lora_wgrad_ws_floats": [C.c_int, C.c_int, C.c_int],
     "tg_gram_fold_rows": [],
     "tg_pca_coef_stats_ws_floats": [C.c_long, C.c_int],
+    "tg_image_metrics_tile": [C.c_int],
+    "tg_image_metrics_ws_doubles": [C.c_long, C.c_int, C.c_int],
 }
 
 TG_BWD_ONE_KERNEL = 1

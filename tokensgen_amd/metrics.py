@@ -1,0 +1,91 @@
+"""How close two videos are, on the GPU: PSNR and SSIM of longvgen/metrics/psnr_ssim.py (`calculate_psnr_pt` :50-79, `calculate_ssim_pt` :159-195, `_ssim_pth` :266-296;
+`rgb2ycbcr_pt` of longvgen/utils/color_util.py:186-208 for the Y channel), for all frames of a clip in ONE call of tg_image_metrics (csrc/metrics.hip): no float64
+copies of the videos, no full-size products, no 121-tap convolutions.  The kernel leaves two float64 numbers per image plane; what is left to torch here is arithmetic
+on those few numbers (one per frame and channel).
+
+    from tokensgen_amd.metrics import calculate_psnr_pt, calculate_ssim_pt, video_metrics, VideoMetrics
+
+`calculate_psnr_pt` / `calculate_ssim_pt` keep the reference's signatures for GPU tensors (n, 3|1, h, w) in [0, 1], fp32 or bf16.  `video_metrics` also takes the
+uint8 frames of `VideoProcessor.postprocess_video(output_type="uint8")` or of a decoder, [B, T, H, W, 3] / [F, H, W, 3], read as `v / 255` exactly.
+
+STATED ASSUMPTION: `cv2.getGaussianKernel(11, 1.5)` is the 11-tap gaussian exp(-(i - 5)^2 / (2 * 1.5^2)) normalised to sum 1 in float64 (cv2 is
+absent here).  STATED DEVIATION: with `test_y_channel` the reference forms Y in the input's dtype (fp32 or bf16); here it is formed in float64.
+
+Not here: `calculate_delta_Eab` (cv2.cvtColor's 8-bit Lab, source absent), LPIPS (VGG weights), the numpy / skimage variants.  Not registered under the `longvgen`
+alias (tokensgen_amd.compat carries hot-path names only).  There is no CPU path."""
+import torch
+
+from . import kernels as K
+
+WINDOW = K.IMAGE_WINDOW
+
+
+def _layout(t):
+    if t.dtype == torch.uint8:
+        if t.dim() in (4, 5) and t.shape[-1] == 3:
+            return "hwc"
+        raise ValueError(f"uint8 frames: expected [F, H, W, 3] or [B, T, H, W, 3], got {tuple(t.shape)}")
+    if t.dim() == 4:
+        return "chw"
+    if t.dim() == 5:
+        return "bcthw"
+    raise ValueError(f"float frames: expected (n, 3|1, h, w) or [B, 3|1, T, H, W], got {tuple(t.shape)}")
+
+
+def video_metrics(a, b, crop_border=0, test_y_channel=False):
+    """Per-frame and pooled PSNR / SSIM of two equally shaped videos on the GPU, from one tg_image_metrics call.
+    a, b: uint8 [B, T, H, W, 3] or [F, H, W, 3] (display bytes, read as v / 255), or fp32 / bf16 in [0, 1] as (n, 3|1, h, w) or [B, 3|1, T, H, W] (views allowed).
+    Returns a dict of float64 device tensors: "mse" (on the [0, 1] scale), "psnr" = 10 log10(1 / (mse + 1e-8)) and "ssim" per frame, shaped [B, T] / [F] / [n]; and the
+    pooled 0-dim "psnr_pooled" = 10 log10(1 / (mean(mse) + 1e-8)) and "ssim_pooled" = mean(ssim): what calculate_psnr_pt / calculate_ssim_pt return for the frames as a
+    batch.  A frame's figures do not depend on the other frames of the call.  Nothing here waits for the device."""
+    assert isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor) and a.shape == b.shape, \
+        f"Image shapes are different: {getattr(a, 'shape', None)}, {getattr(b, 'shape', None)}."
+    out = K.image_metrics(a, b, _layout(a), crop_border, bool(test_y_channel))          # [n_outer, n_inner, planes, 2]
+    if a.dim() == 4:
+        out = out[0]
+    hw = a.shape[-3:-1] if a.dtype == torch.uint8 else a.shape[-2:]
+    h, w = hw[0] - 2 * int(crop_border), hw[1] - 2 * int(crop_border)
+    planes = out.shape[-2]
+    mse = out[..., 0].sum(-1) / (planes * h * w * 255.0 * 255.0)
+    ssim = out[..., 1].sum(-1) / (planes * (h - WINDOW + 1) * (w - WINDOW + 1))
+    return {"mse": mse, "psnr": 10.0 * torch.log10(1.0 / (mse + 1e-8)), "ssim": ssim,
+            "psnr_pooled": 10.0 * torch.log10(1.0 / (mse.mean() + 1e-8)), "ssim_pooled": ssim.mean()}
+
+
+def calculate_psnr_pt(img, img2, crop_border, test_y_channel=False, **kwargs):
+    """psnr_ssim.py:50-79 for GPU tensors (n, 3|1, h, w) in [0, 1]: 10 log10(1 / (mean_n(mse_n) + 1e-8)) as a 0-dim float64 device tensor."""
+    assert img.shape == img2.shape, (f'Image shapes are different: {img.shape}, {img2.shape}.')
+    if img.dim() != 4:
+        raise ValueError(f"expected (n, 3|1, h, w), got {tuple(img.shape)}")
+    return video_metrics(img, img2, crop_border, test_y_channel)["psnr_pooled"]
+
+
+def calculate_ssim_pt(img, img2, crop_border, test_y_channel=False, **kwargs):
+    """psnr_ssim.py:159-195 for GPU tensors (n, 3|1, h, w) in [0, 1]: the mean over images of the per-image SSIM map mean, a 0-dim float64 device tensor."""
+    assert img.shape == img2.shape, (f'Image shapes are different: {img.shape}, {img2.shape}.')
+    if img.dim() != 4:
+        raise ValueError(f"expected (n, 3|1, h, w), got {tuple(img.shape)}")
+    return video_metrics(img, img2, crop_border, test_y_channel)["ssim_pooled"]
+
+
+class VideoMetrics:
+    """Running PSNR / SSIM over many clips (a 25-clip evaluation): `update(a, b)` per clip launches and returns at once, `finalize()` pools every frame seen.
+    Two updates give what one video_metrics call on the concatenated frames gives."""
+
+    def __init__(self, crop_border=0, test_y_channel=False):
+        self.crop_border, self.test_y_channel = crop_border, test_y_channel
+        self._mse, self._ssim = [], []
+
+    def update(self, a, b):
+        m = video_metrics(a, b, self.crop_border, self.test_y_channel)
+        self._mse.append(m["mse"].reshape(-1))
+        self._ssim.append(m["ssim"].reshape(-1))
+        return m
+
+    def finalize(self):
+        """{"frames", "mse", "psnr", "ssim" per frame in update order, "psnr_pooled", "ssim_pooled"}: float64 device tensors (frames: an int)"""
+        if not self._mse:
+            raise RuntimeError("VideoMetrics.finalize: no update yet")
+        mse, ssim = torch.cat(self._mse), torch.cat(self._ssim)
+        return {"frames": mse.numel(), "mse": mse, "psnr": 10.0 * torch.log10(1.0 / (mse + 1e-8)), "ssim": ssim,
+                "psnr_pooled": 10.0 * torch.log10(1.0 / (mse.mean() + 1e-8)), "ssim_pooled": ssim.mean()}
