@@ -719,6 +719,31 @@ int tg_image_metrics_window(double* taps);
 int tg_image_metrics(const void* a, long a_so, long a_si, long a_sc, long a_sr, long a_sp, const void* b, long b_so, long b_si, long b_sc, long b_sr, long b_sp,
                      int dtype, int n_outer, int n_inner, int C, int h, int w, int y_only, double* ws, double* out, hipStream_t stream);
 
+/* LPIPS, VGG16, version 0.1 (csrc/lpips.hip; host side: tokensgen_amd/lpips.py; the definition restated in DESIGN.md §8d): `model(img2, img)` of
+ * longvgen/metrics/lpips.py:12-47 on an lpips.LPIPS(net='vgg') object.  The 12 convolutions above conv1_1 are tg_conv3d_cl (kt = 1, 3 x 3, pad 1, frames as T); these
+ * exports are the rest of the trunk and the distance.  Activations are channels-last bf16 [F][H][W][C].
+ * tg_lpips_conv_in: y[f][i][j][n] = bf16( relu( bias[n] + sum_{c,r,q} weight[n][c][r][q] * s(f, c, i + r - 1, j + q - 1) ) ), n < 64: the ScalingLayer, features.0 and
+ *   features.1 of torchvision's vgg16 and the `.to(float) / 255 * 2 - 1` in front of them.  s = (v - shift[c]) / scale[c] inside the image and 0 outside (the reference
+ *   pads the SCALED tensor), shift = (-0.030, -0.088, -0.188), scale = (0.458, 0.448, 0.450); v = 2 fp32(u / 255) - 1 for dtype 0 (uint8: the quotient rounded to fp32, so that bytes and the fp32
+ *   frames `.float() / 255` with normalize give the same bits), the value itself for dtype 1 (fp32) and 2 (bf16), or 2 v - 1 with normalize = 1 (inputs in [0, 1]; floats only); s is formed in float64 and rounded to fp32 once.  fp32 accumulation: acc = bias, then 27
+ *   fused multiply-adds in the weight's own order.  Pixel (outer, inner, channel, y, x) is element x[outer * so + inner * si + channel * sc + y * sr + x * sp] (strides
+ *   >= 0; a crop is a base offset with a smaller h, w); image f = outer * n_inner + inner.  weight fp32 [64][27], bias fp32 [64], y 16-byte aligned.
+ * tg_relu_cl: x = relu(x) in place on n bf16 elements (n % 8 == 0, 16-byte aligned): F.relu after a convolution whose output feeds the next convolution.  Exact.
+ * tg_relu_maxpool2_cl: y [F][H/2][W/2][C] = F.max_pool2d(F.relu(x), 2, 2) (floor: an odd last row / column is dropped), x [F][H][W][C], C % 8 == 0, H, W >= 2.  Exact,
+ *   F.max_pool2d's scan order included (which of two equal zeros of different sign survives).
+ * tg_lpips_head: out[f] (float64) = sum over the H x W pixels of sum_c w[c] * (a_c / (|a| + 1e-10) - b_c / (|b| + 1e-10))^2, |a| = sqrt(sum_c a_c^2), a / b the pixel's
+ *   feature vectors of fa / fb (relu_on_load = 1: after F.relu): normalize_tensor, the squared difference, the 1 x 1 `lin` convolution and the spatial SUM of
+ *   lpips.LPIPS.forward for one tap; the caller divides by H * W and adds the five taps.  fp32 per element, float64 from the sums over channels on.  C in {64, 128,
+ *   256, 512}; w fp32 [C]; ws: tg_lpips_head_ws_doubles(F, H, W) doubles (one per tile of 512 pixels of a frame); fa, fb 16-byte aligned, ws and out 8-byte.  Two
+ *   launches on `stream` (tiles, then the sum of a frame's tiles in tile order), no atomics: a frame's value does not depend on the other frames of the call; fa == fb
+ *   gives exactly 0; an all-zero vector counts as the zero vector (0 / 1e-10), not NaN. */
+int tg_lpips_conv_in(const void* x, long so, long si, long sc, long sr, long sp, int dtype, int normalize, int n_outer, int n_inner, int h, int w, const float* weight,
+                     const float* bias, void* y, hipStream_t stream);
+int tg_relu_cl(void* x, long n, hipStream_t stream);
+int tg_relu_maxpool2_cl(const void* x, int F, int H, int W, int C, void* y, hipStream_t stream);
+long tg_lpips_head_ws_doubles(int F, int H, int W);
+int tg_lpips_head(const void* fa, const void* fb, const float* w, int F, int H, int W, int C, int relu_on_load, double* ws, double* out, hipStream_t stream);
+
 /* Dispatch overrides for the cross-check tests — NOT part of the operator surface.  The library reads no environment variable and keeps no other
  * process-wide state: the defaults are the shipped path, and these knobs only choose between two PRODUCT kernels of the same operator (each pair is held
  * bitwise or to rounding against each other by tests/).  Knobs: TG_ATTN_PP_MIN_WG (1024: workgroups from which the 8-wave attention kernel is used),

@@ -970,3 +970,84 @@ def image_metrics(a, b, layout, crop_border=0, y_only=False):
     L.check(_launch("image_metrics", lib.tg_image_metrics, pa, *sa, pb, *sb, _IMAGE_DTYPES[a.dtype], n_outer, n_inner, Cn, h, w, int(bool(y_only)), _p(ws), _p(out),
                     _stream()), "tg_image_metrics")
     return out
+
+
+LPIPS_MIN_SIDE = 16            # four floor-mode 2 x 2 pools leave at least one pixel at the last tap
+
+
+def lpips_conv_in(x, layout, weight, bias, out, crop_border=0, normalize=False, outer=None, inner=None):
+    """tg_lpips_conv_in: the pixel ends, the LPIPS scaling layer, conv1_1, bias and ReLU of an image batch -> `out`, bf16 channels-last [F, h, w, 64] (h x w the
+    plane without `crop_border` pixels on every side).  x: uint8 (0..255), fp32 or bf16 (in [-1, 1], or in [0, 1] with normalize) in one of IMAGE_LAYOUTS with 3
+    channels, any view with non-negative strides.  outer: only that outer index; inner = (first, count): only those inner indices (a chunk of a clip: a base offset,
+    no copy); F = the images taken.  weight fp32 [64, 27], bias fp32 [64]."""
+    if not isinstance(x, torch.Tensor) or x.dtype not in _IMAGE_DTYPES:
+        raise TypeError(f"x: expected a uint8, float32 or bfloat16 tensor, got {getattr(x, 'dtype', type(x))}")
+    if layout not in IMAGE_LAYOUTS:
+        raise ValueError(f"layout must be one of {sorted(IMAGE_LAYOUTS)}, got {layout!r}")
+    (n_outer, n_inner, Cn, H, W), st = _image_strides(x, layout)
+    if Cn != 3:
+        raise ValueError(f"expected 3 channels, got {Cn}")
+    cb = int(crop_border)
+    h, w = H - 2 * cb, W - 2 * cb
+    if cb < 0 or h < LPIPS_MIN_SIDE or w < LPIPS_MIN_SIDE:
+        raise ValueError(f"a {H} x {W} image with crop_border {cb} is smaller than {LPIPS_MIN_SIDE} x {LPIPS_MIN_SIDE}")
+    if normalize and x.dtype == torch.uint8:
+        raise ValueError("normalize is for float inputs in [0, 1]; uint8 frames are read as 2 (v / 255) - 1")
+    off = cb * (st[3] + st[4])
+    if outer is not None:
+        if not 0 <= outer < n_outer:
+            raise ValueError(f"outer index {outer} out of range 0..{n_outer - 1}")
+        off, n_outer = off + outer * st[0], 1
+    if inner is not None:
+        first, count = inner
+        if not (0 <= first and count >= 1 and first + count <= n_inner):
+            raise ValueError(f"inner range {inner} out of range 0..{n_inner}")
+        off, n_inner = off + first * st[1], count
+    if n_outer * n_inner < 1:
+        raise ValueError("no images")
+    if tuple(weight.shape) != (64, 27) or tuple(bias.shape) != (64,) or not weight.is_contiguous() or not bias.is_contiguous():
+        raise ValueError(f"weight / bias: expected contiguous [64, 27] / [64], got {tuple(weight.shape)} / {tuple(bias.shape)}")
+    if tuple(out.shape) != (n_outer * n_inner, h, w, 64) or not out.is_contiguous():
+        raise ValueError(f"out: expected contiguous {(n_outer * n_inner, h, w, 64)}, got {tuple(out.shape)}")
+    if not x.is_cuda:
+        raise RuntimeError("lpips_conv_in: expected a GPU tensor (tokensgen_amd has no CPU fallback)")
+    _chk(weight, "weight", torch.float32); _chk(bias, "bias", torch.float32); _chk(out, "out")
+    L.check(_launch("lpips_conv_in", L.load().tg_lpips_conv_in, x.data_ptr() + off * x.element_size(), *st, _IMAGE_DTYPES[x.dtype], int(bool(normalize)), n_outer,
+                    n_inner, h, w, _p(weight), _p(bias), _p(out), _stream()), "tg_lpips_conv_in")
+    return out
+
+
+def relu_cl_(x):
+    """tg_relu_cl: F.relu in place on a contiguous bf16 tensor whose element count is a multiple of 8."""
+    _chk(x, "x")
+    if not x.is_contiguous() or x.numel() % 8 != 0 or x.numel() == 0:
+        raise ValueError(f"x: expected a contiguous tensor with a positive multiple of 8 elements, got {tuple(x.shape)}")
+    L.check(_launch("relu_cl", L.load().tg_relu_cl, _p(x), x.numel(), _stream()), "tg_relu_cl")
+    return x
+
+
+def relu_maxpool2_cl(x):
+    """tg_relu_maxpool2_cl: x bf16 [F, H, W, C] channels-last -> F.max_pool2d(F.relu(x), 2, 2) as [F, H // 2, W // 2, C] (floor)."""
+    _chk(x, "x")
+    if x.dim() != 4 or not x.is_contiguous() or x.shape[0] < 1 or x.shape[1] < 2 or x.shape[2] < 2 or x.shape[3] % 8 != 0 or x.shape[3] == 0:
+        raise ValueError(f"x: expected contiguous [F, H >= 2, W >= 2, C % 8 == 0], got {tuple(x.shape)}")
+    F, H, W, Cn = x.shape
+    y = torch.empty(F, H // 2, W // 2, Cn, dtype=BF16, device=x.device)
+    L.check(_launch("relu_maxpool2_cl", L.load().tg_relu_maxpool2_cl, _p(x), F, H, W, Cn, _p(y), _stream()), "tg_relu_maxpool2_cl")
+    return y
+
+
+def lpips_head(fa, fb, w, relu_on_load=False):
+    """tg_lpips_head: fa, fb bf16 [F, H, W, C] channels-last (C in 64 / 128 / 256 / 512), w fp32 [C] -> float64 [F]: per frame the SUM over the pixels of
+    sum_c w[c] (a_c / (|a| + 1e-10) - b_c / (|b| + 1e-10))^2, the features after F.relu with relu_on_load.  A frame's value does not depend on the other frames."""
+    _chk(fa, "fa"); _chk(fb, "fb"); _chk(w, "w", torch.float32)
+    if fa.dim() != 4 or fa.shape != fb.shape or not fa.is_contiguous() or not fb.is_contiguous() or fa.shape[0] < 1:
+        raise ValueError(f"fa, fb: expected two contiguous [F, H, W, C] tensors of one shape, got {tuple(fa.shape)} and {tuple(fb.shape)}")
+    F, H, W, Cn = fa.shape
+    if Cn not in (64, 128, 256, 512) or tuple(w.shape) != (Cn,):
+        raise ValueError(f"expected C in (64, 128, 256, 512) and w [C], got C = {Cn} and w {tuple(w.shape)}")
+    lib = L.load()
+    ws = torch.empty(lib.tg_lpips_head_ws_doubles(F, H, W), dtype=torch.float64, device=fa.device)
+    out = torch.empty(F, dtype=torch.float64, device=fa.device)
+    L.check(_launch("lpips_head", lib.tg_lpips_head, _p(fa), _p(fb), _p(w), F, H, W, Cn, int(bool(relu_on_load)), _p(ws), _p(out), _stream()), "tg_lpips_head")
+    return out

@@ -77,6 +77,10 @@ PROTOTYPES = {
     "tg_video_to_uint8": [_vp, _l, _l, _l, _i, _i, _i, _i, _vp, _i, _i, _vp],
     "tg_image_metrics_window": [_vp],
     "tg_image_metrics": [_vp, _l, _l, _l, _l, _l, _vp, _l, _l, _l, _l, _l, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp],
+    "tg_lpips_conv_in": [_vp, _l, _l, _l, _l, _l, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "tg_relu_cl": [_vp, _l, _vp],
+    "tg_relu_maxpool2_cl": [_vp, _i, _i, _i, _i, _vp, _vp],
+    "tg_lpips_head": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp],
     "tg_conv3d_cl": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _l, _i, _i, _i, _vp, _vp, _vp, _vp],
     "tg_conv3d_up2_subpixel": [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _l, _i, _vp, _vp, _vp],
     "tg_groupnorm_finalize": [_vp, _l, _i, _f, _vp, _vp],
@@ -116,6 +120,7 @@ QUERIES = {
     "tg_pca_coef_stats_ws_floats": [C.c_long, C.c_int],
     "tg_image_metrics_tile": [C.c_int],
     "tg_image_metrics_ws_doubles": [C.c_long, C.c_int, C.c_int],
+    "tg_lpips_head_ws_doubles": [C.c_int, C.c_int, C.c_int],
 }
 
 TG_BWD_ONE_KERNEL = 1

@@ -11,7 +11,10 @@ uint8 frames of `VideoProcessor.postprocess_video(output_type="uint8")` or of a 
 STATED ASSUMPTION: `cv2.getGaussianKernel(11, 1.5)` is the 11-tap gaussian exp(-(i - 5)^2 / (2 * 1.5^2)) normalised to sum 1 in float64 (cv2 is
 absent here).  STATED DEVIATION: with `test_y_channel` the reference forms Y in the input's dtype (fp32 or bf16); here it is formed in float64.
 
-Not here: `calculate_delta_Eab` (cv2.cvtColor's 8-bit Lab, source absent), LPIPS (VGG weights), the numpy / skimage variants.  Not registered under the `longvgen`
+`calculate_lpips` keeps the signature of longvgen/metrics/lpips.py:12-47 (`model(img2, img)`) for a tokensgen_amd.lpips.LPIPS model; `VideoMetrics(lpips_model=...)`
+carries LPIPS next to the other two (tokensgen_amd/lpips.py).
+
+Not here: `calculate_delta_Eab` (cv2.cvtColor's 8-bit Lab, source absent), the numpy / skimage variants.  Not registered under the `longvgen`
 alias (tokensgen_amd.compat carries hot-path names only).  There is no CPU path."""
 import torch
 
@@ -68,18 +71,40 @@ def calculate_ssim_pt(img, img2, crop_border, test_y_channel=False, **kwargs):
     return video_metrics(img, img2, crop_border, test_y_channel)["ssim_pooled"]
 
 
+def calculate_lpips(img, img2, crop_border, input_order='CHW', test_y_channel=False, model=None, **kwargs):
+    """longvgen/metrics/lpips.py:12-47 for GPU tensors (n, 3, h, w) in [-1, 1], fp32 or bf16: `model(img2, img)` as an (n, 1, 1, 1) float32 DEVICE tensor (the
+    reference moves it to the host).  model: a tokensgen_amd.lpips.LPIPS.  `crop_border` is honoured (the reference's commented-out code meant to; a base offset,
+    no copy); the reference ignores `input_order` and `test_y_channel`: here only 'CHW' and False are accepted."""
+    if model is None:
+        raise ValueError("calculate_lpips: pass model=tokensgen_amd.lpips.LPIPS (the reference's default, None, cannot be called either)")
+    if test_y_channel:
+        raise ValueError("calculate_lpips: LPIPS reads three colour channels; test_y_channel is not supported")
+    if input_order != 'CHW':
+        raise ValueError(f"calculate_lpips: input_order {input_order!r} is not supported: pass (n, 3, h, w)")
+    assert img.shape == img2.shape, (f'Image shapes are different: {img.shape}, {img2.shape}.')
+    if img.dim() != 4 or img.shape[1] != 3:
+        raise ValueError(f"expected (n, 3, h, w), got {tuple(img.shape)}")
+    return model.per_frame(img2, img, "chw", crop_border)[:, 0].sum(0).to(torch.float32).view(-1, 1, 1, 1)
+
+
 class VideoMetrics:
     """Running PSNR / SSIM over many clips (a 25-clip evaluation): `update(a, b)` per clip launches and returns at once, `finalize()` pools every frame seen.
-    Two updates give what one video_metrics call on the concatenated frames gives."""
+    Two updates give what one video_metrics call on the concatenated frames gives.  With lpips_model (a tokensgen_amd.lpips.LPIPS) both also carry "lpips" per frame
+    and "lpips_pooled", the mean over the frames (lpips.video_lpips); without one every key and value is what it was."""
 
-    def __init__(self, crop_border=0, test_y_channel=False):
-        self.crop_border, self.test_y_channel = crop_border, test_y_channel
-        self._mse, self._ssim = [], []
+    def __init__(self, crop_border=0, test_y_channel=False, lpips_model=None):
+        self.crop_border, self.test_y_channel, self.lpips_model = crop_border, test_y_channel, lpips_model
+        self._mse, self._ssim, self._lpips = [], [], []
 
     def update(self, a, b):
         m = video_metrics(a, b, self.crop_border, self.test_y_channel)
         self._mse.append(m["mse"].reshape(-1))
         self._ssim.append(m["ssim"].reshape(-1))
+        if self.lpips_model is not None:
+            from .lpips import video_lpips
+            lp = video_lpips(a, b, self.lpips_model, self.crop_border)
+            m["lpips"], m["lpips_pooled"] = lp["lpips"], lp["lpips_pooled"]
+            self._lpips.append(lp["lpips"].reshape(-1))
         return m
 
     def finalize(self):
@@ -87,5 +112,9 @@ class VideoMetrics:
         if not self._mse:
             raise RuntimeError("VideoMetrics.finalize: no update yet")
         mse, ssim = torch.cat(self._mse), torch.cat(self._ssim)
-        return {"frames": mse.numel(), "mse": mse, "psnr": 10.0 * torch.log10(1.0 / (mse + 1e-8)), "ssim": ssim,
-                "psnr_pooled": 10.0 * torch.log10(1.0 / (mse.mean() + 1e-8)), "ssim_pooled": ssim.mean()}
+        out = {"frames": mse.numel(), "mse": mse, "psnr": 10.0 * torch.log10(1.0 / (mse + 1e-8)), "ssim": ssim,
+               "psnr_pooled": 10.0 * torch.log10(1.0 / (mse.mean() + 1e-8)), "ssim_pooled": ssim.mean()}
+        if self.lpips_model is not None:
+            out["lpips"] = torch.cat(self._lpips)
+            out["lpips_pooled"] = out["lpips"].mean()
+        return out
