@@ -525,3 +525,224 @@ def test_gemm_supported_predicates():
                     assert fn(*case[0]) is case[2 - knob], (fn.__name__, case[0], knob)
         finally:
             L.debug_set("TG_GEMM_W4", old)
+
+
+ATTENTION_PLAN_TABLE = """
+    full 48x2 nq 17776 + rider 226: pp<1,1,0,0,0> grid 3328 block 512 lds 98304 both rows 0+17776 wgs 3360/3456 split 3232+128
+    full 48x2 nq 17776 + rider 226: pp<1,1,0,0,1> grid 256 block 512 lds 98304 both rows 0+17776 wgs 3360/3456 split 3232+128
+    full 48x2 nq 17776 + rider 226: combine(1) grid 512 block 256 lds 0 both rows 0+17776 wgs 3360/3456 split 3232+128
+    full 48x2 nq 17776 + rider 226: pp<1,0,0,1,0> grid 256 block 512 lds 98304 both rows 0+17776 wgs 3360/3456 split 3232+128
+    plain 48x2 nq 17776: pp<0,0,0,0,0> grid 3264 block 512 lds 98304 main rows 0+17408 wgs 3264/3264 split 3264+0
+    plain 48x2 nq 17776: fwd<1> grid 288 block 256 lds 0 main rows 17408+368 wgs 0/0 split 0+0
+    full 48x2 nq 9442: pp<1,1,0,0,0> grid 1728 block 512 lds 98304 main rows 0+9216 wgs 1728/1728 split 1728+0
+    full 48x2 nq 9442: pp<1,0,0,1,0> grid 256 block 512 lds 98304 main rows 0+9216 wgs 1728/1728 split 1728+0
+    full 48x2 nq 9442: fwd<1> grid 192 block 256 lds 0 main rows 9216+226 wgs 0/0 split 0+0
+    plain lse 48x2 nq 17776: pp<0,0,1,0,0> grid 3264 block 512 lds 98304 main rows 0+17408 wgs 3264/3264 split 3264+0
+    plain lse 48x2 nq 17776: fwd<1> grid 288 block 256 lds 0 main rows 17408+368 wgs 0/0 split 0+0
+    full lse 48x2 nq 17776: pp<1,1,1,0,0> grid 3264 block 512 lds 98304 main rows 0+17408 wgs 3264/3264 split 3264+0
+    full lse 48x2 nq 17776: pp<1,0,1,1,0> grid 256 block 512 lds 98304 main rows 0+17408 wgs 3264/3264 split 3264+0
+    full lse 48x2 nq 17776: fwd<1> grid 288 block 256 lds 0 main rows 17408+368 wgs 0/0 split 0+0
+    prescaled lse, no retry 48x2 nq 17776: pp<0,0,1,0,0> grid 3264 block 512 lds 98304 main rows 0+17408 wgs 3264/3264 split 3264+0
+    prescaled lse, no retry 48x2 nq 17776: fwd<1> grid 288 block 256 lds 0 main rows 17408+368 wgs 0/0 split 0+0
+    plain 48x2 nq 6806 2 segments: pp<0,0,0,0,0> grid 1248 block 512 lds 98304 main rows 0+6656 wgs 1248/1248 split 1248+0
+    plain 48x2 nq 6806 2 segments: fwd<1> grid 192 block 256 lds 0 main rows 6656+150 wgs 0/0 split 0+0
+    plain 2x2 nq 700: fwd<1> grid 24 block 256 lds 0 main rows 0+700 wgs 8/8 split 8+0
+    plain 48x2 nq 2816: fwd<2> grid 1056 block 256 lds 0 main rows 0+2816 wgs 576/576 split 576+0
+    plain 1x1 nq 523776 (1023 wgs): fwd<2> grid 2046 block 256 lds 0 main rows 0+523776 wgs 1023/1023 split 1023+0
+    plain 1x1 nq 524288 (1024 wgs): pp<0,0,0,0,0> grid 1024 block 512 lds 98304 main rows 0+524288 wgs 1024/1024 split 1024+0
+    plain 1x1 nq 523777 (1023 full + ragged): pp<0,0,0,0,0> grid 1024 block 512 lds 98304 main rows 0+523777 wgs 1024/1024 split 1024+0
+    plain 2x2 nq 700 pp_min 1: pp<0,0,0,0,0> grid 8 block 512 lds 98304 main rows 0+700 wgs 8/8 split 8+0
+    plain 1x1 nq 261888 (wg256 1023): fwd<1> grid 2046 block 256 lds 0 main rows 0+261888 wgs 512/512 split 512+0
+    plain 1x1 nq 262144 (wg256 1024): fwd<2> grid 1024 block 256 lds 0 main rows 0+262144 wgs 512/512 split 512+0
+    plain 48x2 nq 16996: pp<0,0,0,0,0> grid 3264 block 512 lds 98304 main rows 0+16996 wgs 3264/3264 split 3264+0
+    plain 48x2 nq 17776 + rider 226: pp<0,0,0,0,0> grid 3456 block 512 lds 98304 both rows 0+17776 wgs 3360/3456 split 3456+0
+    full 1x1 nq 524288 (R 0): pp<1,1,0,0,0> grid 1024 block 512 lds 98304 main rows 0+524288 wgs 1024/1024 split 1024+0
+    full 1x1 nq 524288 (R 0): pp<1,0,0,1,0> grid 256 block 512 lds 98304 main rows 0+524288 wgs 1024/1024 split 1024+0
+    full 1x1 nq 575488 (R 100): pp<1,1,0,0,0> grid 1024 block 512 lds 98304 main rows 0+575488 wgs 1124/1124 split 1024+100
+    full 1x1 nq 575488 (R 100): pp<1,1,0,0,1> grid 208 block 512 lds 98304 main rows 0+575488 wgs 1124/1124 split 1024+100
+    full 1x1 nq 575488 (R 100): combine(1) grid 400 block 256 lds 0 main rows 0+575488 wgs 1124/1124 split 1024+100
+    full 1x1 nq 575488 (R 100): pp<1,0,0,1,0> grid 256 block 512 lds 98304 main rows 0+575488 wgs 1124/1124 split 1024+100
+    full 1x1 nq 589824 (R 128): pp<1,1,0,0,0> grid 1024 block 512 lds 98304 main rows 0+589824 wgs 1152/1152 split 1024+128
+    full 1x1 nq 589824 (R 128): pp<1,1,0,0,1> grid 256 block 512 lds 98304 main rows 0+589824 wgs 1152/1152 split 1024+128
+    full 1x1 nq 589824 (R 128): combine(1) grid 512 block 256 lds 0 main rows 0+589824 wgs 1152/1152 split 1024+128
+    full 1x1 nq 589824 (R 128): pp<1,0,0,1,0> grid 256 block 512 lds 98304 main rows 0+589824 wgs 1152/1152 split 1024+128
+    full 1x1 nq 590336 (R 129): pp<1,1,0,0,0> grid 1153 block 512 lds 98304 main rows 0+590336 wgs 1153/1153 split 1153+0
+    full 1x1 nq 590336 (R 129): pp<1,0,0,1,0> grid 256 block 512 lds 98304 main rows 0+590336 wgs 1153/1153 split 1153+0
+    full 8x1 nq 8192 pp_min 1 (128 wgs): pp<1,1,0,0,0> grid 128 block 512 lds 98304 main rows 0+8192 wgs 128/128 split 128+0
+    full 8x1 nq 8192 pp_min 1 (128 wgs): pp<1,0,0,1,0> grid 128 block 512 lds 98304 main rows 0+8192 wgs 128/128 split 128+0
+    full 1x1 nq 131072 pp_min 1 (256 wgs): pp<1,1,0,0,0> grid 256 block 512 lds 98304 main rows 0+131072 wgs 256/256 split 256+0
+    full 1x1 nq 131072 pp_min 1 (256 wgs): pp<1,0,0,1,0> grid 256 block 512 lds 98304 main rows 0+131072 wgs 256/256 split 256+0
+    full 1x1 nq 131584 pp_min 1 (257 wgs): pp<1,1,0,0,0> grid 256 block 512 lds 98304 main rows 0+131584 wgs 257/257 split 256+1
+    full 1x1 nq 131584 pp_min 1 (257 wgs): pp<1,1,0,0,1> grid 16 block 512 lds 98304 main rows 0+131584 wgs 257/257 split 256+1
+    full 1x1 nq 131584 pp_min 1 (257 wgs): combine(1) grid 4 block 256 lds 0 main rows 0+131584 wgs 257/257 split 256+1
+    full 1x1 nq 131584 pp_min 1 (257 wgs): pp<1,0,0,1,0> grid 256 block 512 lds 98304 main rows 0+131584 wgs 257/257 split 256+1
+    full 1x1 nq 512 + rider 132608 pp_min 1 (R 4 > 1): pp<1,1,0,0,0> grid 260 block 512 lds 98304 both rows 0+512 wgs 1/260 split 260+0
+    full 1x1 nq 512 + rider 132608 pp_min 1 (R 4 > 1): pp<1,0,0,1,0> grid 256 block 512 lds 98304 both rows 0+512 wgs 1/260 split 260+0
+    full 1x1 nq 589824 nk 64: pp<1,1,0,0,0> grid 1152 block 512 lds 98304 main rows 0+589824 wgs 1152/1152 split 1152+0
+    full 1x1 nq 589824 nk 64: pp<1,0,0,1,0> grid 256 block 512 lds 98304 main rows 0+589824 wgs 1152/1152 split 1152+0
+    full 1x1 nq 589824 nk 65: pp<1,1,0,0,0> grid 1024 block 512 lds 98304 main rows 0+589824 wgs 1152/1152 split 1024+128
+    full 1x1 nq 589824 nk 65: pp<1,1,0,0,1> grid 256 block 512 lds 98304 main rows 0+589824 wgs 1152/1152 split 1024+128
+    full 1x1 nq 589824 nk 65: combine(1) grid 512 block 256 lds 0 main rows 0+589824 wgs 1152/1152 split 1024+128
+    full 1x1 nq 589824 nk 65: pp<1,0,0,1,0> grid 256 block 512 lds 98304 main rows 0+589824 wgs 1152/1152 split 1024+128
+    full 1x1 nq 589824 split floats 17039360: pp<1,1,0,0,0> grid 1024 block 512 lds 98304 main rows 0+589824 wgs 1152/1152 split 1024+128
+    full 1x1 nq 589824 split floats 17039360: pp<1,1,0,0,1> grid 256 block 512 lds 98304 main rows 0+589824 wgs 1152/1152 split 1024+128
+    full 1x1 nq 589824 split floats 17039360: combine(1) grid 512 block 256 lds 0 main rows 0+589824 wgs 1152/1152 split 1024+128
+    full 1x1 nq 589824 split floats 17039360: pp<1,0,0,1,0> grid 256 block 512 lds 98304 main rows 0+589824 wgs 1152/1152 split 1024+128
+    full 1x1 nq 589824 split floats 17039359: pp<1,1,0,0,0> grid 1152 block 512 lds 98304 main rows 0+589824 wgs 1152/1152 split 1152+0
+    full 1x1 nq 589824 split floats 17039359: pp<1,0,0,1,0> grid 256 block 512 lds 98304 main rows 0+589824 wgs 1152/1152 split 1152+0
+    full lse 1x1 nq 589824: pp<1,1,1,0,0> grid 1152 block 512 lds 98304 main rows 0+589824 wgs 1152/1152 split 1152+0
+    full lse 1x1 nq 589824: pp<1,0,1,1,0> grid 256 block 512 lds 98304 main rows 0+589824 wgs 1152/1152 split 1152+0
+    full 48x2 nq 17776 + rider 226 split 0: pp<1,1,0,0,0> grid 3456 block 512 lds 98304 both rows 0+17776 wgs 3360/3456 split 3456+0
+    full 48x2 nq 17776 + rider 226 split 0: pp<1,0,0,1,0> grid 256 block 512 lds 98304 both rows 0+17776 wgs 3360/3456 split 3456+0
+    full 48x2 nq 17776 + rider 226 fixedm 0: pp<1,0,0,0,0> grid 3328 block 512 lds 98304 both rows 0+17776 wgs 3360/3456 split 3232+128
+    full 48x2 nq 17776 + rider 226 fixedm 0: pp<1,0,0,0,1> grid 256 block 512 lds 98304 both rows 0+17776 wgs 3360/3456 split 3232+128
+    full 48x2 nq 17776 + rider 226 fixedm 0: combine(0) grid 512 block 256 lds 0 both rows 0+17776 wgs 3360/3456 split 3232+128
+    full 48x2 nq 17776 + rider 226, a segment without bound: pp<1,0,0,0,0> grid 3328 block 512 lds 98304 both rows 0+17776 wgs 3360/3456 split 3232+128
+    full 48x2 nq 17776 + rider 226, a segment without bound: pp<1,0,0,0,1> grid 256 block 512 lds 98304 both rows 0+17776 wgs 3360/3456 split 3232+128
+    full 48x2 nq 17776 + rider 226, a segment without bound: combine(0) grid 512 block 256 lds 0 both rows 0+17776 wgs 3360/3456 split 3232+128
+    full 48x2 nq 17776 + rider 226, no retry: pp<1,0,0,0,0> grid 3328 block 512 lds 98304 both rows 0+17776 wgs 3360/3456 split 3232+128
+    full 48x2 nq 17776 + rider 226, no retry: pp<1,0,0,0,1> grid 256 block 512 lds 98304 both rows 0+17776 wgs 3360/3456 split 3232+128
+    full 48x2 nq 17776 + rider 226, no retry: combine(0) grid 512 block 256 lds 0 both rows 0+17776 wgs 3360/3456 split 3232+128
+    full 48x2 nq 17776 + rider 226, not prescaled: pp<0,0,0,0,0> grid 3328 block 512 lds 98304 both rows 0+17776 wgs 3360/3456 split 3232+128
+    full 48x2 nq 17776 + rider 226, not prescaled: pp<0,0,0,0,1> grid 256 block 512 lds 98304 both rows 0+17776 wgs 3360/3456 split 3232+128
+    full 48x2 nq 17776 + rider 226, not prescaled: combine(0) grid 512 block 256 lds 0 both rows 0+17776 wgs 3360/3456 split 3232+128
+    full 48x4 nq 3172: pp<1,1,0,0,0> grid 1024 block 512 lds 98304 main rows 0+3072 wgs 1152/1152 split 1024+128
+    full 48x4 nq 3172: pp<1,1,0,0,1> grid 256 block 512 lds 98304 main rows 0+3072 wgs 1152/1152 split 1024+128
+    full 48x4 nq 3172: combine(1) grid 512 block 256 lds 0 main rows 0+3072 wgs 1152/1152 split 1024+128
+    full 48x4 nq 3172: pp<1,0,0,1,0> grid 256 block 512 lds 98304 main rows 0+3072 wgs 1152/1152 split 1024+128
+    full 48x4 nq 3172: fwd<1> grid 192 block 256 lds 0 main rows 3072+100 wgs 0/0 split 0+0
+    plain 2x2 nq 700 + rider 226: fwd<1> grid 24 block 256 lds 0 main rows 0+700 wgs 8/8 split 8+0
+    plain 2x2 nq 700 + rider 226: fwd<1> grid 8 block 256 lds 0 rider rows 0+226 wgs 4/4 split 4+0
+    full 48x2 nq 2816 + rider 17776: fwd<2> grid 1056 block 256 lds 0 main rows 0+2816 wgs 576/576 split 576+0
+    full 48x2 nq 2816 + rider 17776: pp<1,0,0,0,0> grid 3264 block 512 lds 98304 rider rows 0+17408 wgs 3264/3264 split 3264+0
+    full 48x2 nq 2816 + rider 17776: fwd<1> grid 288 block 256 lds 0 rider rows 17408+368 wgs 0/0 split 0+0
+    fwd nq 0: error -2: tg_attention_fwd: bad shape nq=0 nk1=64
+    fwd nq 1: ok
+    fwd nk1 0: error -2: tg_attention_fwd: bad shape nq=64 nk1=0
+    fwd heads 0: error -2: tg_attention_fwd: bad shape nq=64 nk1=64
+    fwd batch 0: error -2: tg_attention_fwd: bad shape nq=64 nk1=64
+    multi 1x1 nq 1 nk 1: ok
+    multi heads 0: error -2: tg_attention_fwd_multi: bad shape
+    multi batch 0: error -2: tg_attention_fwd_multi: bad shape
+    multi nq 0: error -1: tg_attention_fwd_multi: problem 0
+    multi nseg 0: error -1: tg_attention_fwd_multi: problem 0
+    multi nseg 2: ok
+    multi nseg 3: error -1: tg_attention_fwd_multi: problem 0
+    multi segment 1 nk 0: error -2: tg_attention: problem 0 segment 1: nk=0
+    multi segment 2 nk 0: error -2: tg_attention: problem 0 segment 2: nk=0
+    multi segment 1 nk 64 vt_ld 64: ok
+    multi segment 1 nk 65 vt_ld 64: error -2: tg_attention: problem 0 segment 1: vt_ld must cover nk rounded up to 64
+    multi segment 1 nk 65 vt_ld 128: ok
+    multi segment 2 nk 65 vt_ld 64: error -2: tg_attention: problem 0 segment 2: vt_ld must cover nk rounded up to 64
+    multi per-item scales batch 16: ok
+    multi per-item scales batch 17: error -2: tg_attention_fwd_multi: per-item segment-2 scales for at most 16 batch items (got 17)
+    multi one scale batch 17: ok
+    multi rider nq 1: ok
+    multi rider nq 0: error -1: tg_attention_fwd_multi: problem 1 must have one key segment
+    multi rider nseg 2: error -1: tg_attention_fwd_multi: problem 1 must have one key segment
+    multi rider nk 0: error -2: tg_attention: problem 1: nk=0
+    multi rider nk 65 vt_ld 64: error -2: tg_attention: problem 1: vt_ld must cover nk rounded up to 64
+    multi 48x2 nq 17776 + rider 226 retry 3457: ok
+    multi 48x2 nq 17776 + rider 226 retry 3456: error -2: tg_attention_fwd_multi: retry workspace of 3456 ints, need 3457 (tg_attention_retry_ints)
+    lse nq 1: ok
+    lse nq 0: error -2: tg_attention_fwd_lse: bad shape nq=0 nk=64
+    lse nk 0: error -2: tg_attention_fwd_lse: bad shape nq=64 nk=0
+    lse nk 65 vt_ld 64: error -2: tg_attention: segment: vt_ld must cover nk rounded up to 64
+    lse_ex heads 0: error -2: tg_attention_fwd_lse_ex: bad shape nq=64 nk=64
+    lse_ex batch 0: error -2: tg_attention_fwd_lse_ex: bad shape nq=64 nk=64
+    lse_ex 48x2 nq 17776 retry 3361: ok
+    lse_ex 48x2 nq 17776 retry 3360: error -2: tg_attention_fwd_lse_ex: retry workspace of 3360 ints, need 3361 (tg_attention_retry_ints)
+    layout nq 17776 nk 17776 heads 48 batch 2: seed 0 lse 6825984 d 8532480 cnt 10238984 ncnt 1708032 xmask 11947016 dq_part 11947112 total 11947120
+    layout nq 480 nk 18256 heads 48 batch 2: seed 0 lse 184320 d 230400 cnt 276488 ncnt 46080 xmask 322568 dq_part 322664 total 23915636
+    layout nq 1 nk 1 heads 1 batch 1: seed 0 lse 4 d 5 cnt 16 ncnt 32 xmask 48 dq_part 52 total 571
+    layout nq 33 nk 7 heads 3 batch 1: seed 0 lse 396 d 495 cnt 604 ncnt 192 xmask 796 dq_part 800 total 51497
+    layout nq 65536 nk 64 heads 1 batch 1: seed 0 lse 262144 d 327680 cnt 393224 ncnt 65536 xmask 458760 dq_part 458764 total 34013205
+    layout nq 65537 nk 64 heads 1 batch 1: seed 0 lse 262148 d 327685 cnt 393232 ncnt 65568 xmask 458800 dq_part 458804 total 458807
+    48x2 17776x17776 flag: problem 0: one kernel stats 70x96 wgs_k 6720 kparts 1 dq 0 join 0
+    48x2 17776x17776 flag: fused grid 6720 block 512 lds 116736 main 0 rider -1 main_wgs 6720
+    48x2 17776x17776: problem 0: two launches stats 70x96 wgs_k 6720 kparts 1 dq 6720 join 0
+    48x2 17776x17776 flag dq unaligned: problem 0: two launches stats 70x96 wgs_k 6720 kparts 1 dq 6720 join 0
+    47x2 17776x17776 flag: problem 0: two launches stats 70x94 wgs_k 6580 kparts 1 dq 6580 join 0
+    48x2 8928x17776 flag (279 tiles): problem 0: two launches stats 35x96 wgs_k 6720 kparts 1 dq 3360 join 0
+    48x2 8929x17776 flag (280 tiles): problem 0: one kernel stats 35x96 wgs_k 6720 kparts 1 dq 0 join 0
+    48x2 8929x17776 flag (280 tiles): fused grid 6720 block 512 lds 116736 main 0 rider -1 main_wgs 6720
+    48x2 480x18256 flag: problem 0: two launches stats 2x96 wgs_k 6912 kparts 8 dq 1536 join 2880
+    48x2 480x18256 dq unaligned: problem 0: two launches stats 2x96 wgs_k 6912 kparts 1 dq 192 join 0
+    32x8 256x4096 (256 blocks): problem 0: two launches stats 1x256 wgs_k 4096 kparts 6 dq 1536 join 4096
+    257x1 256x4096 (257 blocks): problem 0: two launches stats 1x257 wgs_k 4112 kparts 1 dq 257 join 0
+    48x2 480x1536 (48 key tiles): problem 0: two launches stats 2x96 wgs_k 576 kparts 3 dq 576 join 2880
+    48x2 480x992 (31 key tiles): problem 0: two launches stats 2x96 wgs_k 384 kparts 1 dq 192 join 0
+    48x2 main + vip-key flag: problem 0: one kernel stats 70x96 wgs_k 6720 kparts 1 dq 0 join 0
+    48x2 main + vip-key flag: problem 1: one kernel stats 70x96 wgs_k 192 kparts 1 dq 0 join 0
+    48x2 main + vip-key flag: fused grid 6912 block 512 lds 116736 main 0 rider 1 main_wgs 6720
+    48x2 main + vip-query flag: problem 0: one kernel stats 70x96 wgs_k 6720 kparts 1 dq 0 join 0
+    48x2 main + vip-query flag: problem 1: two launches stats 2x96 wgs_k 6912 kparts 8 dq 1536 join 2880
+    48x2 main + vip-query flag: fused grid 6720 block 512 lds 116736 main 0 rider -1 main_wgs 6720
+    48x2 vip-query + main flag: problem 0: two launches stats 2x96 wgs_k 6912 kparts 8 dq 1536 join 2880
+    48x2 vip-query + main flag: problem 1: one kernel stats 70x96 wgs_k 6720 kparts 1 dq 0 join 0
+    48x2 vip-query + main flag: fused grid 6720 block 512 lds 116736 main 1 rider -1 main_wgs 6720
+    48x2 main + vip-key: problem 0: two launches stats 70x96 wgs_k 6720 kparts 1 dq 6720 join 0
+    48x2 main + vip-key: problem 1: two launches stats 70x96 wgs_k 192 kparts 1 dq 6720 join 0
+"""
+
+
+def test_attention_plan_table():
+    """tokensgen_amd/csrc/attention_plan.h: the launches of the forward entry points (kernel, grid, block, LDS bytes, the rows covered, the derived AttnParams fields:
+    `wgs main_wgs/total_wgs`, `split split_first+nsplit`), the shapes they refuse (code and text), every offset of the backward's workspace, and the backward's form and
+    grids, as pure host functions printed by tests/attention_plan_table (tests/csrc/attention_plan_table.cpp: the cases; 256 CUs).  The expectations are worked out by
+    hand from the conditions of the launchers this header replaced: the workload's shapes, then a case on each side of every threshold — 1024 workgroups of 512 and of
+    256 rows, the ragged tail with and without a saved round and with a rider, the split remainder at 0 / 128 / 129 and a launch within one round, one / two key tiles,
+    the split workspace one float short, every condition of the constant shift — and for the backward the one-kernel conditions, the dQ split and its clamps, and two
+    problems.  pp<PRESCALED,FIXEDM,LSE,RETRY,SPLIT>; the running-max log-sum-exp kernel is pp<0,0,1,0,0> for prescaled K too (scale_log2 is 1 there)."""
+    import subprocess
+    exe = os.path.join(ROOT, "tests", "attention_plan_table")
+    assert os.path.exists(exe), "build first: python -c 'import __graft_entry__ as g; g.build()'"
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr[-2000:]
+    got, want = r.stdout.splitlines(), [ln.strip() for ln in ATTENTION_PLAN_TABLE.strip().splitlines()]
+    assert len(got) == len(want)
+    for g, w in zip(got, want):
+        assert g == w
+
+
+def test_attention_size_functions_keep_their_formulas():
+    """tg_attention_retry_ints, tg_attention_split_floats and tg_attention_bwd_ws_floats answer from attention_plan.h; callers allocate by them.  Held here to the
+    formulas the three functions had before, written out (256 CUs: what the library assumes without a GPU, and the MI355X's count), around the thresholds: query rows at
+    multiples of 512, 256 and 32 and one to each side, launches of at most one round, remainders at 0 / 128 / 129, the dQ partials at 256 / 257 query blocks."""
+    from tokensgen_amd import lib as L
+    lib = L.load()
+    n_cu = 256
+    half = 512 * (64 + 2 + 64)
+
+    def wgs(nq0, nq1, heads, batch):
+        return ((nq0 + 511) // 512 + ((nq1 + 511) // 512 if nq1 > 0 else 0)) * heads * batch
+
+    def retry_ints(nq0, nq1, heads, batch):
+        return 1 + wgs(nq0, nq1, heads, batch)
+
+    def split_floats(nq0, nq1, heads, batch):
+        g = wgs(nq0, nq1, heads, batch)
+        R = g % n_cu
+        return 2 * R * half if (g > n_cu and R > 0 and 2 * R <= n_cu) else 0
+
+    def bwd_ws_floats(nq, nk, heads, batch):
+        split = (nq + 255) // 256 * heads * batch <= 256
+        return (6 * batch * heads * nq + 8 + batch * heads * ((nq + 31) // 32) * 32 + 8 + batch * heads + (8 * batch * nq * heads * 64 + 4 if split else 0))
+
+    fwd = [(17776, 226, 48, 2), (17776, 0, 48, 2), (17550, 226, 48, 2), (9442, 0, 48, 2), (6806, 0, 48, 2), (700, 0, 2, 2), (700, 226, 2, 2), (2816, 0, 48, 2),
+           (1, 0, 1, 1), (1, 1, 1, 1), (512, 0, 1, 1), (513, 0, 1, 1), (511, 512, 3, 5), (512, -3, 7, 1),
+           (131072, 0, 1, 1), (131073, 0, 1, 1), (130560, 512, 1, 1), (131072, 512, 1, 1),                   # 256 / 257 workgroups: within one round or not
+           (524288, 0, 1, 1), (575488, 0, 1, 1), (589312, 0, 1, 1), (589824, 0, 1, 1), (590336, 0, 1, 1),     # R = 0, 100, 127, 128, 129
+           (512 * 12, 0, 48, 4), (3172, 0, 48, 4), (512 * 128, 0, 8, 1), (512 * 144, 0, 8, 1), (512 * 145, 0, 8, 1), (512 * 144, 8 * 512, 8, 1),
+           (17776, 17776, 48, 2), (512, 132608, 1, 1), (4096, 4096, 24, 1)]
+    for case in fwd:
+        assert lib.tg_attention_retry_ints(*case) == retry_ints(*case), case
+        assert lib.tg_attention_split_floats(*case) == split_floats(*case), case
+    assert lib.tg_attention_split_floats(17776, 226, 48, 2) == 2 * 128 * half and lib.tg_attention_split_floats(589824, 0, 1, 1) == 2 * 128 * half
+    assert lib.tg_attention_split_floats(590336, 0, 1, 1) == 0 and lib.tg_attention_split_floats(131072, 0, 1, 1) == 0
+    bwd = [(17776, 17776, 48, 2), (480, 18256, 48, 2), (17776, 480, 48, 2), (17550, 17550, 48, 2), (1, 1, 1, 1), (2, 1, 1, 1), (3, 5, 1, 1), (31, 7, 3, 1), (32, 7, 3, 1),
+           (33, 7, 3, 1), (255, 64, 2, 3), (256, 64, 2, 3), (257, 64, 2, 3), (65536, 64, 1, 1), (65537, 64, 1, 1), (256, 4096, 32, 8), (256, 4096, 257, 1),
+           (257, 4096, 32, 4), (257, 4096, 32, 5), (512, 100, 128, 1), (513, 100, 128, 1), (300, 330, 6, 2), (700, 700, 2, 2), (8928, 17776, 48, 2), (8929, 17776, 48, 2)]
+    for case in bwd:
+        assert lib.tg_attention_bwd_ws_floats(*case) == bwd_ws_floats(*case), case
+    assert lib.tg_attention_bwd_ws_floats(17776, 17776, 48, 2) == 11947120 and lib.tg_attention_bwd_ws_floats(480, 18256, 48, 2) == 23915636

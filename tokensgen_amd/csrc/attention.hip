@@ -22,13 +22,15 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "attention_plan.h"
 #include "common.h"
 #include "tokensgen_hip.h"
 
 namespace {
 
-constexpr int KVBLK = 64;
-constexpr int TILE_B = 64 * 128;   // one 64x64 bf16 tile
+using attn_cfg::KVBLK;
+using attn_cfg::SPLIT_HALF_FLOATS;
+using attn_cfg::TILE_B;
 
 struct Seg {
     const bf16_t* q; long q_ld, q_sb;
@@ -60,12 +62,11 @@ struct AttnParams {
     // "this workgroup's constant-shift result had a row sum below 2^-64" flag the verification raises and the RETRY launch consumes
     int* retry;
     // key-axis split of the launch's LAST `nsplit` workgroups (wgids split_first .. total_wgs - 1): each runs as two half-length workgroups
-    // that leave (unnormalised O, m, l) partials in split_ws, joined by attn_split_combine_kernel — see attention_launch
+    // that leave (unnormalised O, m, l) partials in split_ws, joined by attn_split_combine_kernel — see attn_fwd_dispatch (attention_plan.h)
     int split_first, nsplit;
     float* split_ws;
     long split_ws_floats;
 };
-constexpr long SPLIT_HALF_FLOATS = 512L * (64 + 2 + 64);     // per half: O [512][64], m [512], l [512], O2 [512][64] (second half of a 2-segment parent)
 
 // plain fmaxf nests: clang fuses them to v_max3_f32 (built with -fno-honor-nans so MFMA outputs are not canonicalised by an
 // extra v_max first); inline-asm versions get an s_nop after every dependent op and measured ~1.5 % slower
@@ -317,7 +318,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnParams p) {
 // epilogue VERIFIES (row sum >= 2^-64, i.e. the largest weight >= 2^-79: the terms flushed below 2^-126 are then < 2^-32 of the sum) —
 // a workgroup with a failing row raises its flag in p.retry and the RETRY launch (running maximum; a one-workgroup-per-CU grid that walks
 // the flag list) recomputes exactly those workgroups.  The per-tile max chain / vote / rescale (15 % of the launch) is gone from the hot loop.
-// SPLIT: the launch of the half-length workgroups of the split tail (see attention_launch) — its own instantiation so that the partial-result
+// SPLIT: the launch of the half-length workgroups of the split tail (see attn_fwd_dispatch, attention_plan.h) — its own instantiation so that the partial-result
 // epilogue and the runtime tile range stay out of the ordinary kernel's register allocation (as one kernel they cost it ~45 spilled VGPRs)
 template <bool PRESCALED, int FIXEDM = 0, bool LSE = false, bool RETRY = false, bool SPLIT = false>
 __global__ __launch_bounds__(512) void attn_fwd_pp_kernel(AttnParams p) {
@@ -841,183 +842,148 @@ __global__ __launch_bounds__(256) void attn_split_combine_kernel(AttnParams p, i
     if (bad) p.retry[1 + wgid] = 1;
 }
 
-}  // namespace
-
-static int attention_launch(AttnParams& p, float scale, int k_prescaled, const char* who, hipStream_t stream) {
-    const int nq = p.nq, heads = p.heads, batch = p.batch;
-    // k_prescaled: K rows already carry scale*log2(e) (written by tg_qk_layernorm_rope with out_scale), `scale` is then ignored
-    p.prescaled = k_prescaled ? 1 : 0;
-    p.scale_log2 = k_prescaled ? 1.0f : scale * 1.4426950408889634f;
-    // kernel choice by query-range length: the 8-wave ping-pong kernel from `pp_min` workgroups of 512 rows (4 per CU) on; below that the
-    // 4-wave kernel with 256-row tiles (2 query blocks per wave) while those still give >= 4 workgroups per CU, else 128-row tiles.
-    // Measured on MI355X at N = 17776: ping-pong 1.12-1.18 PFLOP/s, 256-row tiles 0.90, 128-row tiles 0.85.
-    const long wg256 = (long)((nq + 255) / 256) * heads * batch;
-    const long pp_min = tg_knob(TG_KNOB_ATTN_PP_MIN_WG);    // 1024; the cross-check tests lower it (tg_debug_set)
-    const long wg512 = (long)((nq + 511) / 512) * heads * batch;
-    const bool pp = wg512 >= pp_min;
-    if (p.r_nq > 0 && !pp) {
-        // the rider needs the ping-pong kernel: run it as a launch of its own through the ordinary dispatch
-        AttnParams r{};
-        r.s[0] = p.r_s; r.nseg = 1;
-        r.out = p.r_out; r.o_ld = p.r_o_ld; r.o_sb = p.r_o_sb;
-        r.nq = p.r_nq; r.heads = heads; r.batch = batch;
-        p.r_nq = 0;
-        const int rc = attention_launch(p, scale, k_prescaled, who, stream);
-        return rc ? rc : attention_launch(r, scale, k_prescaled, who, stream);
-    }
-    const int n_cu = tg_device_cus();
-    // ---- ragged last query tile: every ping-pong workgroup takes the same time, so a launch of G workgroups costs ceil(G / CUs) rounds.
-    // When dropping the ragged last tile of every (head, batch) saves a round, those rows go to the 4-wave kernel in 128-row workgroups
-    // right behind the ping-pong launch (same stream): N = 17776 without a rider 7.69 -> 7.53 ms, the T2To stage's N = 9442 (19 -> 18
-    // tiles: 8 -> 7 rounds).  With a rider problem the riders already fill the last round, and the split loses (measured 8.0 vs 7.75 ms).
-    const int full_rows = (nq / 512) * 512;
-    const long wg_full = (long)(nq / 512) * heads * batch;
-    if (pp && p.r_nq == 0 && full_rows < nq && wg_full >= pp_min && (wg_full + n_cu - 1) / n_cu < (wg512 + n_cu - 1) / n_cu) {
-        AttnParams m = p;                                   // the full 512-row tiles: ping-pong kernel
-        m.nq = full_rows;
-        const int rc = attention_launch(m, scale, k_prescaled, who, stream);
-        if (rc) return rc;
-        AttnParams t = p;                                   // the ragged remainder: 128-row workgroups of the 4-wave kernel
-        t.nq = nq - full_rows;
-        for (int sg = 0; sg < p.nseg; ++sg) t.s[sg].q = p.s[sg].q + (long)full_rows * p.s[sg].q_ld;
-        t.out = p.out + (long)full_rows * p.o_ld;
-        if (p.lse) t.lse = p.lse + full_rows;
-        const int nqt = (t.nq + 127) / 128;
-        hipLaunchKernelGGL(attn_fwd_kernel<1>, dim3((unsigned)(nqt * heads * batch)), dim3(256), 0, stream, t);
-        TG_LAUNCH_CHECK(who);
-        return TG_OK;
-    }
-    // constant-shift softmax (attn_fwd_pp_kernel<.., FIXEDM = 1>): every segment of a k_prescaled launch carries the key-norm bound and the
-    // caller gave a retry workspace.  The TG_ATTN_FIXEDM knob = 0 (tg_debug_set) forces the running-max kernel.
-    const bool fixedm_on = tg_knob(TG_KNOB_ATTN_FIXEDM) != 0;
-    bool fixedm = fixedm_on && p.prescaled && pp && p.retry;
-    for (int sg = 0; sg < p.nseg && fixedm; ++sg) fixedm = p.s[sg].kn2 != nullptr;
-    if (fixedm && p.r_nq > 0) fixedm = p.r_s.kn2 != nullptr;
-    p.main_wgs = (int)wg512;
-    const long grid512 = wg512 + (p.r_nq > 0 ? (long)((p.r_nq + 511) / 512) * heads * batch : 0);
-    p.total_wgs = (int)grid512;
-    const unsigned retry_grid = (unsigned)(grid512 < n_cu ? grid512 : n_cu);
-    // ---- last-round quantisation: every 512-row workgroup of a launch takes the same time (same key length), so G workgroups cost
-    // ceil(G / CUs) rounds — the DiT's 3360 + 96 = 13.5 x 256 pay for 14.  When the remainder R = G mod CUs is at most half a round, R
-    // workgroups are split over the KEY axis into 2 R half-length workgroups (their own launch behind the G - R whole ones, partials joined by
-    // attn_split_combine_kernel): the tail then costs half a round, 13.5 instead of 14.  Splitting over the queries cannot do that (DESIGN §8:
-    // 128-row workgroups are themselves badly quantised).  The split parents are the last R workgroups of the MAIN problem, not the riders:
-    // the halves of one head's query tiles share that head's K / V in their XCD's L2, whereas every rider has a (batch, head) of its own and
-    // 256 of those streaming at once are HBM-bound.  The TG_ATTN_SPLIT knob = 0 disables; needs the caller's split workspace.
-    const bool split_on = tg_knob(TG_KNOB_ATTN_SPLIT) != 0;
-    p.nsplit = 0;
-    p.split_first = (int)grid512;
-    if (pp && split_on && p.split_ws && !p.lse && grid512 > n_cu) {
-        const long R = grid512 % n_cu;
-        const int nt_main = (p.s[0].nk + KVBLK - 1) / KVBLK;
-        if (R > 0 && 2 * R <= n_cu && R <= wg512 && nt_main >= 2 && p.split_ws_floats >= 2 * R * SPLIT_HALF_FLOATS) {
-            p.nsplit = (int)R;
-            p.split_first = (int)(wg512 - R);
-        }
-    }
-    // whole workgroups | halves of the split parents (rounded up to whole groups of 16 = 8 XCDs x 2 halves)
-    const unsigned main_grid = (unsigned)(grid512 - p.nsplit), split_grid = (unsigned)(16 * ((p.nsplit + 7) / 8));
-    constexpr size_t PP_LDS = 4 * TILE_B + 8 * 8192;
-    // launch one instantiation of the ping-pong kernel (96 KiB of dynamic LDS: the attribute is set once per instantiation AND device)
-#define TG_PP(GRID, ...)                                                                                                            \
-    do {                                                                                                                            \
-        TG_DYN_LDS((attn_fwd_pp_kernel<__VA_ARGS__>), 4 * TILE_B + 8 * 8192);                                                       \
-        hipLaunchKernelGGL((attn_fwd_pp_kernel<__VA_ARGS__>), dim3(GRID), dim3(512), PP_LDS, stream, p);                            \
-    } while (0)
-    if (pp && fixedm) {
-        // the verified constant-shift pass, [the split tail and its join,] then the retry launch: a persistent grid that re-runs the flagged
-        // workgroups (normally none)
-        if (p.lse) {
-            TG_PP(main_grid, true, 1, true);
-            TG_PP(retry_grid, true, 0, true, true);
-        } else {
-            TG_PP(main_grid, true, 1);
-            if (p.nsplit) {
-                TG_PP(split_grid, true, 1, false, false, true);
-                hipLaunchKernelGGL(attn_split_combine_kernel, dim3((unsigned)(4 * p.nsplit)), dim3(256), 0, stream, p, 1);
+// one launch of the plan: the kernel id -> its instantiation (96 KiB of dynamic LDS for the ping-pong kernel: the attribute is set once per
+// instantiation AND device)
+int launch_one(const AttnLaunch& l, const AttnParams& a, const char* who, hipStream_t stream) {
+    const dim3 grid(l.grid), block((unsigned)l.block);
+#define TG_PP(...)                                                                                              \
+    case attn_pp_id(__VA_ARGS__):                                                                               \
+        TG_DYN_LDS((attn_fwd_pp_kernel<__VA_ARGS__>), attn_cfg::PP_LDS_BYTES);                                  \
+        hipLaunchKernelGGL((attn_fwd_pp_kernel<__VA_ARGS__>), grid, block, (size_t)l.lds, stream, a);           \
+        break
+    switch (l.kernel) {
+        case ATTN_K_FWD1: hipLaunchKernelGGL(attn_fwd_kernel<1>, grid, block, 0, stream, a); break;
+        case ATTN_K_PP:
+            // <PRESCALED, FIXEDM, LSE, RETRY, SPLIT>.  The code object holds the instantiations in the order of their first mention: keep it, and a
+            // change to this file can be checked by comparing the device assembly
+            switch (l.pp) {
+                TG_PP(true, 1, true, false, false);
+                TG_PP(true, 0, true, true, false);
+                TG_PP(true, 1, false, false, false);
+                TG_PP(true, 1, false, false, true);
+                TG_PP(true, 0, false, true, false);
+                TG_PP(false, 0, true, false, false);
+                TG_PP(true, 0, false, false, false);
+                TG_PP(true, 0, false, false, true);
+                TG_PP(false, 0, false, false, false);
+                TG_PP(false, 0, false, false, true);
+                default: return tg_set_error(TG_ERR_ARG, "%s: no ping-pong kernel %d", who, l.pp);
             }
-            TG_PP(retry_grid, true, 0, false, true);
-        }
-    } else if (pp) {
-        if (p.lse) {
-            TG_PP(main_grid, false, 0, true);
-        } else if (p.prescaled) {
-            TG_PP(main_grid, true);
-            if (p.nsplit) TG_PP(split_grid, true, 0, false, false, true);
-        } else {
-            TG_PP(main_grid, false);
-            if (p.nsplit) TG_PP(split_grid, false, 0, false, false, true);
-        }
-        if (p.nsplit) hipLaunchKernelGGL(attn_split_combine_kernel, dim3((unsigned)(4 * p.nsplit)), dim3(256), 0, stream, p, 0);
-    } else if (wg256 >= 1024) {
-        hipLaunchKernelGGL(attn_fwd_kernel<2>, dim3((unsigned)wg256), dim3(256), 0, stream, p);
-    } else {
-        const int nqt = (nq + 127) / 128;
-        hipLaunchKernelGGL(attn_fwd_kernel<1>, dim3((unsigned)(nqt * heads * batch)), dim3(256), 0, stream, p);
+            break;
+        case ATTN_K_FWD2: hipLaunchKernelGGL(attn_fwd_kernel<2>, grid, block, 0, stream, a); break;
+        case ATTN_K_COMBINE: hipLaunchKernelGGL(attn_split_combine_kernel, grid, block, 0, stream, a, l.fixedm); break;
     }
 #undef TG_PP
     TG_LAUNCH_CHECK(who);
     return TG_OK;
 }
 
+// the parameter block of one launch: the sub-problem it covers and the plan's derived fields
+AttnParams launch_params(const AttnParams& p, const AttnLaunch& l) {
+    AttnParams a{};
+    if (l.cover == ATTN_RIDER) {                              // the rider as a single-segment problem of its own
+        a.s[0] = p.r_s; a.nseg = 1;
+        a.out = p.r_out; a.o_ld = p.r_o_ld; a.o_sb = p.r_o_sb;
+        a.heads = p.heads; a.batch = p.batch;
+        a.scale_log2 = p.scale_log2; a.prescaled = p.prescaled;
+    } else {
+        a = p;
+        if (l.cover == ATTN_MAIN) a.r_nq = 0;
+    }
+    for (int sg = 0; sg < a.nseg; ++sg) a.s[sg].q += (long)l.row0 * a.s[sg].q_ld;
+    a.out += (long)l.row0 * a.o_ld;
+    if (a.lse) a.lse += l.row0;
+    a.nq = l.rows;
+    a.main_wgs = l.main_wgs; a.total_wgs = l.total_wgs; a.split_first = l.split_first; a.nsplit = l.nsplit;
+    return a;
+}
+
+}  // namespace
+
+// p: the problem as the caller gave it (attention_fwd); the launches are attn_fwd_plan's (attention_plan.h), under the live knobs and CU count
+static int attention_launch(const AttnParams& p, AttnEntry entry, hipStream_t stream) {
+    AttnFwdShape s{};
+    s.nq = p.nq; s.r_nq = p.r_nq; s.heads = p.heads; s.batch = p.batch; s.nseg = p.nseg; s.nk1 = p.s[0].nk;
+    s.prescaled = p.prescaled != 0; s.lse = p.lse != nullptr; s.retry = p.retry != nullptr;
+    s.kn2_all = p.r_nq == 0 || p.r_s.kn2 != nullptr;
+    for (int sg = 0; sg < p.nseg; ++sg) s.kn2_all = s.kn2_all && p.s[sg].kn2 != nullptr;
+    s.split_floats = p.split_ws ? p.split_ws_floats : 0;
+    const AttnKnobs knobs{tg_knob(TG_KNOB_ATTN_PP_MIN_WG), (int)tg_knob(TG_KNOB_ATTN_FIXEDM), (int)tg_knob(TG_KNOB_ATTN_SPLIT)};
+    const AttnFwdPlan pl = attn_fwd_plan(s, knobs, tg_device_cus());
+    for (int i = 0; i < pl.n; ++i) {
+        const int rc = launch_one(pl.l[i], launch_params(p, pl.l[i]), attn_entry_name(entry), stream);
+        if (rc) return rc;
+    }
+    return TG_OK;
+}
+
+extern "C" long tg_attention_retry_ints(int nq0, int nq1, int heads, int batch) { return attn_retry_ints(nq0, nq1, heads, batch); }
+
+// An upper bound for callers that size the workspace once: it knows neither nk, nor the knobs, nor whether the shape reaches the ping-pong kernel, all of
+// which can only take the split away (attn_fwd_dispatch).
+extern "C" long tg_attention_split_floats(int nq0, int nq1, int heads, int batch) {
+    return attn_split_floats(attn_split_remainder(attn_grid512(nq0, nq1, heads, batch), tg_device_cus()));
+}
+
 static int fill_segment(Seg& S, const tg_attn_segment& g, const char* what) {
     TG_REQUIRE(g.q && g.k && g.vt, TG_ERR_ARG, "tg_attention: %s: null pointer", what);
-    TG_REQUIRE(g.nk > 0, TG_ERR_SHAPE, "tg_attention: %s: nk=%d", what, g.nk);
     TG_REQUIRE(g.q_ld % 8 == 0 && g.k_ld % 8 == 0 && g.vt_ld % 64 == 0 && g.q_strideB % 8 == 0 && g.k_strideB % 8 == 0 && tg_aligned16(g.q) &&
                tg_aligned16(g.k) && tg_aligned16(g.vt), TG_ERR_ALIGN, "tg_attention: %s alignment", what);
-    TG_REQUIRE(g.vt_ld >= ((g.nk + 63) / 64) * 64, TG_ERR_SHAPE, "tg_attention: %s: vt_ld must cover nk rounded up to 64", what);
     S = Seg{(const bf16_t*)g.q, g.q_ld, g.q_strideB, (const bf16_t*)g.k, g.k_ld, g.k_strideB, (const bf16_t*)g.vt, g.vt_ld, g.nk, g.k_norm2_max};
     return TG_OK;
 }
 
-extern "C" long tg_attention_retry_ints(int nq0, int nq1, int heads, int batch) {
-    return 1 + (long)((nq0 + 511) / 512 + (nq1 > 0 ? (nq1 + 511) / 512 : 0)) * heads * batch;
-}
-
-extern "C" long tg_attention_split_floats(int nq0, int nq1, int heads, int batch) {
-    int dev = 0, n_cu = 256;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
-    const long g = (long)((nq0 + 511) / 512 + (nq1 > 0 ? (nq1 + 511) / 512 : 0)) * heads * batch;
-    const long R = g % n_cu;
-    return (g > n_cu && R > 0 && 2 * R <= n_cu) ? 2 * R * SPLIT_HALF_FLOATS : 0;
+// What the three forward entry points share: the pointer and alignment checks, the shape refusals (attn_fwd_refusal), the parameter block, the launches.
+// lse: the training forward's log-sum-exp output (one problem of one segment), or null.
+static int attention_fwd(AttnEntry entry, const tg_attn_problem* problems, int nproblems, int heads, int batch, float scale, int k_prescaled,
+                         const tg_attn_workspace* ws, float* lse, hipStream_t stream) {
+    const char* who = attn_entry_name(entry);
+    const tg_attn_problem& A = problems[0];
+    TG_REQUIRE(A.out, TG_ERR_ARG, "%s: problem 0", who);
+    TG_REQUIRE(A.out_ld % 8 == 0 && A.out_strideB % 8 == 0 && tg_aligned16(A.out), TG_ERR_ALIGN, "%s: output alignment (16 B)", who);
+    AttnParams p{};
+    AttnFwdDims d{};
+    d.nq = A.nq; d.heads = heads; d.batch = batch; d.nseg = A.nseg;
+    int rc;
+    for (int sg = 0; sg < (A.nseg == 2 ? 2 : 1); ++sg) {
+        if ((rc = fill_segment(p.s[sg], A.seg[sg], attn_seg_name(entry, false, sg)))) return rc;
+        d.seg[sg] = AttnSegDims{A.seg[sg].nk, A.seg[sg].vt_ld};
+    }
+    d.per_item_scales = A.seg2_scale_batch != nullptr;
+    if (nproblems == 2) {
+        const tg_attn_problem& B = problems[1];
+        TG_REQUIRE(B.out, TG_ERR_ARG, "%s: problem 1 must have one key segment", who);
+        TG_REQUIRE(B.out_ld % 8 == 0 && B.out_strideB % 8 == 0 && tg_aligned16(B.out), TG_ERR_ALIGN, "%s: output alignment (16 B)", who);
+        if ((rc = fill_segment(p.r_s, B.seg[0], attn_seg_name(entry, true, 0)))) return rc;
+        d.rider = true; d.r_nq = B.nq; d.r_nseg = B.nseg; d.r_seg = AttnSegDims{B.seg[0].nk, B.seg[0].vt_ld};
+        p.r_out = (bf16_t*)B.out; p.r_o_ld = B.out_ld; p.r_o_sb = B.out_strideB; p.r_nq = B.nq;
+    }
+    if (ws && ws->retry) {
+        d.retry = true; d.retry_ints = ws->retry_ints;
+        p.retry = ws->retry;
+    }
+    if (ws && ws->split) {
+        TG_REQUIRE(tg_aligned16(ws->split), TG_ERR_ALIGN, "%s: split workspace alignment (16 B)", who);
+        p.split_ws = ws->split;
+        p.split_ws_floats = ws->split_floats;
+    }
+    const AttnRefusal no = attn_fwd_refusal(entry, d);
+    if (no.err) return tg_set_error(no.err, "%s", no.msg);
+    p.nseg = A.nseg;
+    for (int i = 0; i < 16; ++i) p.seg2_scale_b[i] = A.seg2_scale_batch ? A.seg2_scale_batch[i < batch ? i : batch - 1] : A.seg2_scale;
+    p.out = (bf16_t*)A.out; p.o_ld = A.out_ld; p.o_sb = A.out_strideB;
+    p.nq = A.nq; p.heads = heads; p.batch = batch;
+    // k_prescaled: K rows already carry scale*log2(e) (written by tg_qk_layernorm_rope with out_scale), `scale` is then ignored
+    p.prescaled = k_prescaled ? 1 : 0;
+    p.scale_log2 = k_prescaled ? 1.0f : scale * 1.4426950408889634f;
+    p.lse = lse; p.lse_rows = lse ? A.nq : 0;
+    return attention_launch(p, entry, stream);
 }
 
 extern "C" int tg_attention_fwd_multi(const tg_attn_problem* problems, int nproblems, int heads, int batch, float scale, int k_prescaled,
                                       const tg_attn_workspace* ws, hipStream_t stream) {
     TG_REQUIRE(problems && (nproblems == 1 || nproblems == 2), TG_ERR_ARG, "tg_attention_fwd_multi: 1 or 2 problems");
-    TG_REQUIRE(heads > 0 && batch > 0, TG_ERR_SHAPE, "tg_attention_fwd_multi: bad shape");
-    const tg_attn_problem& A = problems[0];
-    TG_REQUIRE(A.out && A.nq > 0 && (A.nseg == 1 || A.nseg == 2), TG_ERR_ARG, "tg_attention_fwd_multi: problem 0");
-    TG_REQUIRE(A.out_ld % 8 == 0 && A.out_strideB % 8 == 0 && tg_aligned16(A.out), TG_ERR_ALIGN, "tg_attention_fwd_multi: output alignment (16 B)");
-    AttnParams p{};
-    int rc = fill_segment(p.s[0], A.seg[0], "problem 0 segment 1");
-    if (rc) return rc;
-    p.nseg = A.nseg;
-    if (A.nseg == 2 && (rc = fill_segment(p.s[1], A.seg[1], "problem 0 segment 2"))) return rc;
-    TG_REQUIRE(!A.seg2_scale_batch || batch <= 16, TG_ERR_SHAPE, "tg_attention_fwd_multi: per-item segment-2 scales for at most 16 batch items (got %d)", batch);
-    for (int i = 0; i < 16; ++i) p.seg2_scale_b[i] = A.seg2_scale_batch ? A.seg2_scale_batch[i < batch ? i : batch - 1] : A.seg2_scale;
-    p.out = (bf16_t*)A.out; p.o_ld = A.out_ld; p.o_sb = A.out_strideB;
-    p.nq = A.nq; p.heads = heads; p.batch = batch;
-    if (nproblems == 2) {
-        const tg_attn_problem& B = problems[1];
-        TG_REQUIRE(B.out && B.nq > 0 && B.nseg == 1, TG_ERR_ARG, "tg_attention_fwd_multi: problem 1 must have one key segment");
-        TG_REQUIRE(B.out_ld % 8 == 0 && B.out_strideB % 8 == 0 && tg_aligned16(B.out), TG_ERR_ALIGN, "tg_attention_fwd_multi: output alignment (16 B)");
-        if ((rc = fill_segment(p.r_s, B.seg[0], "problem 1"))) return rc;
-        p.r_out = (bf16_t*)B.out; p.r_o_ld = B.out_ld; p.r_o_sb = B.out_strideB; p.r_nq = B.nq;
-    }
-    if (ws && ws->retry) {
-        TG_REQUIRE(ws->retry_ints >= tg_attention_retry_ints(p.nq, p.r_nq, heads, batch), TG_ERR_SHAPE,
-                   "tg_attention_fwd_multi: retry workspace of %ld ints, need %ld (tg_attention_retry_ints)", ws->retry_ints,
-                   tg_attention_retry_ints(p.nq, p.r_nq, heads, batch));
-        p.retry = ws->retry;
-    }
-    if (ws && ws->split) {
-        TG_REQUIRE(tg_aligned16(ws->split), TG_ERR_ALIGN, "tg_attention_fwd_multi: split workspace alignment (16 B)");
-        p.split_ws = ws->split;
-        p.split_ws_floats = ws->split_floats;
-    }
-    return attention_launch(p, scale, k_prescaled, "tg_attention_fwd_multi", stream);
+    return attention_fwd(ATTN_FWD_MULTI, problems, nproblems, heads, batch, scale, k_prescaled, ws, nullptr, stream);
 }
 
 extern "C" int tg_attention_fwd(const void* q1, long q1_ld, long q1_strideB,
@@ -1027,7 +993,10 @@ extern "C" int tg_attention_fwd(const void* q1, long q1_ld, long q1_strideB,
                                 float seg2_scale, void* out, long out_ld, long out_strideB,
                                 int nq, int heads, int batch, float scale, int k_prescaled, hipStream_t stream) {
     TG_REQUIRE(q1 && k1 && vt1 && out, TG_ERR_ARG, "tg_attention_fwd: null pointer");
-    TG_REQUIRE(nq > 0 && nk1 > 0 && heads > 0 && batch > 0, TG_ERR_SHAPE, "tg_attention_fwd: bad shape nq=%d nk1=%d", nq, nk1);
+    AttnFwdDims d{};
+    d.nq = nq; d.heads = heads; d.batch = batch; d.seg[0].nk = nk1;
+    const AttnRefusal no = attn_fwd_refusal(ATTN_FWD, d);
+    if (no.err) return tg_set_error(no.err, "%s", no.msg);
     tg_attn_problem A{};
     A.seg[0] = tg_attn_segment{q1, q1_ld, q1_strideB, k1, k1_ld, k1_strideB, vt1, vt1_ld, nk1, nullptr};
     A.nseg = 1;
@@ -1041,42 +1010,31 @@ extern "C" int tg_attention_fwd(const void* q1, long q1_ld, long q1_strideB,
     return tg_attention_fwd_multi(&A, 1, heads, batch, scale, k_prescaled, nullptr, stream);
 }
 
-extern "C" int tg_attention_fwd_lse(const void* q, long q_ld, long q_strideB, const void* k, long k_ld, long k_strideB, const void* vt, long vt_ld, int nk,
-                                    void* out, long out_ld, long out_strideB, int nq, int heads, int batch, float scale, float* lse, hipStream_t stream) {
-    TG_REQUIRE(q && k && vt && out && lse, TG_ERR_ARG, "tg_attention_fwd_lse: null pointer");
-    TG_REQUIRE(nq > 0 && nk > 0 && heads > 0 && batch > 0, TG_ERR_SHAPE, "tg_attention_fwd_lse: bad shape nq=%d nk=%d", nq, nk);
-    TG_REQUIRE(out_ld % 8 == 0 && out_strideB % 8 == 0 && tg_aligned16(out), TG_ERR_ALIGN, "tg_attention_fwd_lse: output alignment (16 B)");
-    AttnParams p{};
-    const tg_attn_segment g{q, q_ld, q_strideB, k, k_ld, k_strideB, vt, vt_ld, nk, nullptr};
-    int rc = fill_segment(p.s[0], g, "segment");
-    if (rc) return rc;
-    p.nseg = 1;
-    p.out = (bf16_t*)out; p.o_ld = out_ld; p.o_sb = out_strideB;
-    p.nq = nq; p.heads = heads; p.batch = batch;
-    p.lse = lse; p.lse_rows = nq;
-    return attention_launch(p, scale, 0, "tg_attention_fwd_lse", stream);
-}
-
 // tg_attention_fwd_lse on the inference path's fast kernels: K rows that already carry scale * log2(e) (k_prescaled) and, with the key-norm bound
 // of tg_qk_layernorm_rope_pair_kmax + a retry workspace, the verified constant-shift softmax (attn_fwd_pp_kernel<true, 1, LSE> + its retry launch).
+static int attention_fwd_lse(AttnEntry entry, const void* q, long q_ld, long q_strideB, const void* k, long k_ld, long k_strideB, const void* vt, long vt_ld, int nk,
+                             void* out, long out_ld, long out_strideB, int nq, int heads, int batch, float scale, int k_prescaled, const float* k_norm2_max,
+                             int* retry, long retry_ints, float* lse, hipStream_t stream) {
+    TG_REQUIRE(q && k && vt && out && lse, TG_ERR_ARG, "%s: null pointer", attn_entry_name(entry));
+    tg_attn_problem A{};
+    A.seg[0] = tg_attn_segment{q, q_ld, q_strideB, k, k_ld, k_strideB, vt, vt_ld, nk, k_norm2_max};
+    A.nseg = 1;
+    A.out = out; A.out_ld = out_ld; A.out_strideB = out_strideB; A.nq = nq;
+    tg_attn_workspace ws{};
+    ws.retry = retry; ws.retry_ints = retry_ints;
+    return attention_fwd(entry, &A, 1, heads, batch, scale, k_prescaled, &ws, lse, stream);
+}
+
+extern "C" int tg_attention_fwd_lse(const void* q, long q_ld, long q_strideB, const void* k, long k_ld, long k_strideB, const void* vt, long vt_ld, int nk,
+                                    void* out, long out_ld, long out_strideB, int nq, int heads, int batch, float scale, float* lse, hipStream_t stream) {
+    return attention_fwd_lse(ATTN_FWD_LSE, q, q_ld, q_strideB, k, k_ld, k_strideB, vt, vt_ld, nk, out, out_ld, out_strideB, nq, heads, batch, scale, 0, nullptr, nullptr,
+                             0, lse, stream);
+}
+
 extern "C" int tg_attention_fwd_lse_ex(const void* q, long q_ld, long q_strideB, const void* k, long k_ld, long k_strideB, const void* vt, long vt_ld, int nk,
                                        void* out, long out_ld, long out_strideB, int nq, int heads, int batch, float scale, int k_prescaled,
                                        const float* k_norm2_max, int* retry, long retry_ints, float* lse, hipStream_t stream) {
-    TG_REQUIRE(q && k && vt && out && lse, TG_ERR_ARG, "tg_attention_fwd_lse_ex: null pointer");
-    TG_REQUIRE(nq > 0 && nk > 0 && heads > 0 && batch > 0, TG_ERR_SHAPE, "tg_attention_fwd_lse_ex: bad shape nq=%d nk=%d", nq, nk);
-    TG_REQUIRE(out_ld % 8 == 0 && out_strideB % 8 == 0 && tg_aligned16(out), TG_ERR_ALIGN, "tg_attention_fwd_lse_ex: output alignment (16 B)");
-    AttnParams p{};
-    const tg_attn_segment g{q, q_ld, q_strideB, k, k_ld, k_strideB, vt, vt_ld, nk, k_norm2_max};
-    int rc = fill_segment(p.s[0], g, "segment");
-    if (rc) return rc;
-    p.nseg = 1;
-    p.out = (bf16_t*)out; p.o_ld = out_ld; p.o_sb = out_strideB;
-    p.nq = nq; p.heads = heads; p.batch = batch;
-    p.lse = lse; p.lse_rows = nq;
-    if (retry) {
-        TG_REQUIRE(retry_ints >= tg_attention_retry_ints(nq, 0, heads, batch), TG_ERR_SHAPE,
-                   "tg_attention_fwd_lse_ex: retry workspace of %ld ints, need %ld (tg_attention_retry_ints)", retry_ints, tg_attention_retry_ints(nq, 0, heads, batch));
-        p.retry = retry;
-    }
-    return attention_launch(p, scale, k_prescaled, "tg_attention_fwd_lse_ex", stream);
+    return attention_fwd_lse(ATTN_FWD_LSE_EX, q, q_ld, q_strideB, k, k_ld, k_strideB, vt, vt_ld, nk, out, out_ld, out_strideB, nq, heads, batch, scale, k_prescaled,
+                             k_norm2_max, retry, retry_ints, lse, stream);
 }
+

@@ -12,6 +12,7 @@
 #include <type_traits>
 
 #include "attention_bwd.h"
+#include "attention_plan.h"
 #include "tokensgen_hip.h"
 
 namespace {
@@ -109,9 +110,8 @@ __device__ __forceinline__ uint2 lds_tr_b64(const bf16_t* p) {
     return r;
 }
 
-constexpr int BT = 32;                     // rows of the streamed tile
-constexpr int LQ2 = 72;                    // [row][d] tile: row stride in elements (144 B)
-constexpr int ROWT_EL = BT * LQ2;
+// the tile and LDS sizes that the kernels share with their launches: attention_plan.h
+using namespace attn_cfg;
 
 struct Bwd2Params {
     BwdParams p;
@@ -671,8 +671,6 @@ struct FusedParams {
     int* r_xmask;
     int main_wgs;        // workgroups of the main call; the grid is main_wgs + (r.nq > 0 ? rider workgroups : 0)
 };
-constexpr int DSLD = 40;                 // dS^T tile row stride in elements (80 B: 8-byte aligned 4-query runs)
-constexpr int DQLD = 68;                 // dQ tile row stride in floats (272 B: the 16 lanes of a block column land on different banks)
 
 // The counters and the dQ blocks are exchanged between workgroups of ONE XCD, whose L2 is the coherence point.  What the kernel uses, and what
 // tg_attention_bwd_probe checks on the device before a caller may select this form: dQ lines are read with PLAIN 16-byte loads behind one
@@ -712,12 +710,6 @@ __device__ __forceinline__ void cnt_write(int* c, int v) { asm volatile("global_
 // fragments for every caller (bf16(k * scale_log2): no multiply anywhere) — the forward had used the unrounded K, and the gradient error of such calls doubled (dV 2.3e-3 -> 4.9e-3).
 // =================================================================================================================================
 constexpr int PP_EXTRA = 3;
-constexpr int PP_RING = 4;
-constexpr int PP_ST_BYTES = 2 * PP_RING * ROWT_EL * 2;          // Q | dO tiles
-constexpr int PP_SEED_BYTES = PP_RING * 64 * 16;
-constexpr int PP_DS_SLOT = 256 * DSLD * 2;                      // one dS^T tile [256 keys][DSLD] bf16
-constexpr int PP_DQ_SLOT = BT * DQLD * 4;                       // one dQ partial [32 q][DQLD] fp32
-constexpr int PP_LDS = PP_ST_BYTES + PP_SEED_BYTES + 2 * PP_DS_SLOT + 4 * PP_DQ_SLOT;
 
 // global accesses of the vector segment: wave-uniform 64-bit base in SGPRs + a 32-bit lane offset.  A tile step is then ONE scalar add — VALU instructions
 // are the currency of Y (the partner wave's MFMA stream owns the issue port: ~13 cycles per VALU instruction there)
@@ -1155,17 +1147,8 @@ __global__ __launch_bounds__(64) void fused_probe_kernel(int* bad, int* cnt, flo
 
 }  // namespace
 
-// statistics: 2 floats per query row (log-sum-exp unless the forward kept it, and D) + the 16-byte seed row of the dK/dV kernel
-// key-axis split of the dQ launch: only for calls with so few query blocks that one workgroup per block leaves most of the chip idle
-constexpr int DQ_SPLIT_MAX = 8;
-static inline bool dq_split_shape(int nq, int heads, int batch) { return (long)((nq + 255) / 256) * heads * batch <= 256; }
-static inline long dq_split_floats(int nq, int heads, int batch) { return dq_split_shape(nq, heads, batch) ? (long)DQ_SPLIT_MAX * batch * nq * heads * HD + 4 : 0; }
-
-extern "C" long tg_attention_bwd_ws_floats(int nq, int nk, int heads, int batch) {
-    (void)nk;
-    return 6L * batch * heads * nq + 8 + (long)batch * heads * ((nq + BT - 1) / BT) * 32 + 8 + (long)batch * heads     // + the one-kernel form's dQ counters and per-head XCD masks
-           + dq_split_floats(nq, heads, batch);                                                                           // + the dQ launch's key-range partials (few queries only)
-}
+// the workspace of one problem: attn_bwd_layout (attention_plan.h) has every offset
+extern "C" long tg_attention_bwd_ws_floats(int nq, int nk, int heads, int batch) { return attn_bwd_layout(nq, nk, heads, batch).total; }
 
 // The device probe of the one-kernel form (fused_probe_kernel) as explicit entry points on CALLER-owned memory: nothing is allocated, freed or
 // synchronised inside the ABI.  The caller zero-fills nothing (the call clears the buffer itself, asynchronously), copies the buffer to the host once the
@@ -1216,13 +1199,13 @@ extern "C" int tg_attention_bwd_ex(const void* q, long q_ld, long q_sb, const vo
 namespace {
 struct Prepared {
     Bwd2Params pp;
-    dim3 gq, gk;
-    bool one_kernel;
-    int* cnt;
-    long ncnt;
+    int* cnt;            // the one-kernel form's exchange counters, the per-head XCD masks behind them: zeroed together
+    int* xmask;
+    size_t zero_bytes;
+    float* dq_part;      // the dQ launch's key-range partials
 };
-// validation + parameter block of one problem; decides the form (one kernel / two launches) exactly as documented for tg_attention_bwd_ex
-int bwd_prepare(const tg_attn_bwd_problem& a, int heads, int batch, int flags, Prepared& out) {
+// validation + parameter block of one problem, its pointers into the workspace from attn_bwd_layout
+int bwd_prepare(const tg_attn_bwd_problem& a, int heads, int batch, Prepared& out) {
     const int accumulate = a.accumulate == 1 ? 3 : (a.accumulate & 3);      // bit 0: dq, bit 1: dk and dv; 1 = all three (the original meaning of the flag)
     TG_REQUIRE(a.q && a.k && a.v && a.o && a.dout && a.dq && a.dk && (a.dv || a.dv_bf16) && a.ws, TG_ERR_ARG, "tg_attention_bwd: null pointer");
     TG_REQUIRE(a.dv || !(accumulate & 2), TG_ERR_ARG, "tg_attention_bwd: accumulate into dv needs the fp32 dv");
@@ -1232,22 +1215,19 @@ int bwd_prepare(const tg_attn_bwd_problem& a, int heads, int batch, int flags, P
                a.k_ld % 8 == 0 && a.v_ld % 8 == 0 && a.o_ld % 8 == 0 && a.do_ld % 8 == 0 && a.q_sb % 8 == 0 && a.k_sb % 8 == 0 && a.v_sb % 8 == 0 && a.o_sb % 8 == 0 &&
                a.do_sb % 8 == 0, TG_ERR_ALIGN, "tg_attention_bwd: q/k/v/o/dO need 16-byte aligned rows");
     const int nq = a.nq, nk = a.nk;
-    const long nrow = (long)batch * heads * nq;               // workspace: seed rows (16 B each, first: alignment) | log-sum-exp | D
+    const AttnBwdLayout L = attn_bwd_layout(nq, nk, heads, batch);
     out.pp.p = BwdParams{(const bf16_t*)a.q, (const bf16_t*)a.k, (const bf16_t*)a.v, (const bf16_t*)a.o, (const bf16_t*)a.dout, a.q_ld, a.q_sb, a.k_ld, a.k_sb, a.v_ld,
-                         a.v_sb, a.o_ld, a.o_sb, a.do_ld, a.do_sb, a.dq, a.dk, a.dv, a.dq_ld, a.dq_sb, a.dk_ld, a.dk_sb, a.dv_ld, a.dv_sb, a.ws + 4 * nrow, a.ws + 5 * nrow,
-                         (uint4*)a.ws, nq, nk, heads, batch, a.scale * 1.4426950408889634f, a.scale, accumulate, a.lse ? 1 : 0, (bf16_t*)a.dv_bf16, a.dv_bf16_ld, a.dv_bf16_sb};
+                         a.v_sb, a.o_ld, a.o_sb, a.do_ld, a.do_sb, a.dq, a.dk, a.dv, a.dq_ld, a.dq_sb, a.dk_ld, a.dk_sb, a.dv_ld, a.dv_sb, a.ws + L.lse, a.ws + L.d,
+                         (uint4*)(a.ws + L.seed), nq, nk, heads, batch, a.scale * 1.4426950408889634f, a.scale, accumulate, a.lse ? 1 : 0, (bf16_t*)a.dv_bf16, a.dv_bf16_ld,
+                         a.dv_bf16_sb};
     if (a.lse) out.pp.p.lse = const_cast<float*>(a.lse);
     out.pp.kparts = 1;
     out.pp.dq_part = nullptr;
+    out.dq_part = a.ws + L.dq_part;
     if (fabsf(out.pp.p.scale_log2 - 1.0f) < 4e-7f) out.pp.p.scale_log2 = 1.0f;      // ln 2 * log2 e: exactly one
-    out.gq = dim3((unsigned)((nq + 255) / 256), (unsigned)(batch * heads));
-    out.gk = dim3((unsigned)((nk + 255) / 256), (unsigned)(batch * heads));
-    // the ordered dQ accumulation runs the key blocks of a head as a chain a few tiles apart: worth it only when there are many more query tiles than
-    // key blocks (the 17776^2 call: 556 tiles, 70 blocks; the vip queries' call with 15 tiles and 72 blocks would serialise)
-    const bool chain_ok = (long)((nq + BT - 1) / BT) >= 4L * out.gk.x && a.dq_ld % 4 == 0 && a.dq_sb % 4 == 0 && tg_aligned16(a.dq);
-    out.one_kernel = (flags & TG_BWD_ONE_KERNEL) && chain_ok && ((heads * batch) & 7) == 0;
-    out.cnt = (int*)(a.ws + ((6 * nrow + 8 + 3) & ~3L));
-    out.ncnt = (long)batch * heads * ((nq + BT - 1) / BT) * 32;       // the exchange counters; the per-head XCD masks sit behind them
+    out.cnt = (int*)(a.ws + L.cnt);
+    out.xmask = (int*)(a.ws + L.xmask);
+    out.zero_bytes = (size_t)(L.ncnt + (long)batch * heads) * sizeof(int);
     return TG_OK;
 }
 }  // namespace
@@ -1256,52 +1236,43 @@ extern "C" int tg_attention_bwd_multi(const tg_attn_bwd_problem* problems, int c
     TG_REQUIRE(problems && count >= 1 && count <= 2, TG_ERR_ARG, "tg_attention_bwd_multi: one or two problems");
     TG_REQUIRE(!(flags & TG_BWD_ONE_KERNEL) || status, TG_ERR_ARG, "tg_attention_bwd_ex: TG_BWD_ONE_KERNEL needs the status words");
     Prepared P[2];
+    AttnBwdShape shapes[2];
     for (int i = 0; i < count; ++i) {
-        const int rc = bwd_prepare(problems[i], heads, batch, flags, P[i]);
+        const tg_attn_bwd_problem& a = problems[i];
+        const int rc = bwd_prepare(a, heads, batch, P[i]);
         if (rc) return rc;
+        shapes[i] = AttnBwdShape{a.nq, a.nk, a.dq_ld % 4 == 0 && a.dq_sb % 4 == 0 && tg_aligned16(a.dq)};
     }
-    for (int i = 0; i < count; ++i) hipLaunchKernelGGL(attn_bwd_stats2_kernel, P[i].gq, dim3(256), 0, stream, P[i].pp.p);
+    // the form of every problem (one kernel / two launches) exactly as documented for tg_attention_bwd_ex, and every grid: attn_bwd_plan (attention_plan.h)
+    const AttnBwdPlan pl = attn_bwd_plan(shapes, count, heads, batch, flags, tg_device_cus());
+    for (int i = 0; i < count; ++i) hipLaunchKernelGGL(attn_bwd_stats2_kernel, dim3(pl.pr[i].stats_x, pl.pr[i].stats_y), dim3(256), 0, stream, P[i].pp.p);
     // one-kernel problems: the first is the main call, a second one rides in the same launch (its workgroups behind the main call's: they fill the last round)
-    int main_i = -1, rider_i = -1;
-    for (int i = 0; i < count; ++i)
-        if (P[i].one_kernel) { if (main_i < 0) main_i = i; else rider_i = i; }
-    if (main_i >= 0) {
+    if (pl.main_i >= 0) {
+        const Prepared& M = P[pl.main_i];
         FusedParams fp{};
-        fp.p = P[main_i].pp.p; fp.cnt = P[main_i].cnt; fp.status = status; fp.xmask = P[main_i].cnt + P[main_i].ncnt;
-        fp.main_wgs = (int)(P[main_i].gk.x * P[main_i].gk.y);
-        unsigned grid = (unsigned)fp.main_wgs;
-        hipError_t e = hipMemsetAsync(fp.cnt, 0, (size_t)(P[main_i].ncnt + (long)batch * heads) * sizeof(int), stream);
-        if (e == hipSuccess && rider_i >= 0) {
-            fp.r = P[rider_i].pp.p; fp.r_cnt = P[rider_i].cnt; fp.r_xmask = P[rider_i].cnt + P[rider_i].ncnt;
-            grid += P[rider_i].gk.x * P[rider_i].gk.y;
-            e = hipMemsetAsync(fp.r_cnt, 0, (size_t)(P[rider_i].ncnt + (long)batch * heads) * sizeof(int), stream);
+        fp.p = M.pp.p; fp.cnt = M.cnt; fp.status = status; fp.xmask = M.xmask;
+        fp.main_wgs = pl.fused_main_wgs;
+        hipError_t e = hipMemsetAsync(fp.cnt, 0, M.zero_bytes, stream);
+        if (e == hipSuccess && pl.rider_i >= 0) {
+            const Prepared& R = P[pl.rider_i];
+            fp.r = R.pp.p; fp.r_cnt = R.cnt; fp.r_xmask = R.xmask;
+            e = hipMemsetAsync(fp.r_cnt, 0, R.zero_bytes, stream);
         }
         if (e != hipSuccess) return tg_set_error(TG_ERR_HIP - (int)e, "tg_attention_bwd_ex: %s", hipGetErrorString(e));
         TG_DYN_LDS(attn_bwd_fused_pp_kernel, PP_LDS);
-        hipLaunchKernelGGL(attn_bwd_fused_pp_kernel, dim3(grid), dim3(512), PP_LDS, stream, fp);
+        hipLaunchKernelGGL(attn_bwd_fused_pp_kernel, dim3(pl.fused_grid), dim3(512), PP_LDS, stream, fp);
         TG_LAUNCH_CHECK("tg_attention_bwd(one kernel)");
     }
     for (int i = 0; i < count; ++i) {
-        if (P[i].one_kernel) continue;
-        hipLaunchKernelGGL(attn_bwd_dkdv7_kernel, dim3(P[i].gk.x * P[i].gk.y), dim3(512), 0, stream, P[i].pp);
-        // dQ: one workgroup per 256 queries and head — or, with few queries, per (256 queries, head, key range): ~3 rounds of the chip's resident slots (2 per CU)
-        const BwdParams& bp = P[i].pp.p;
-        const long wgs = (long)P[i].gq.x * P[i].gq.y, ntile = (bp.nk + BT - 1) / BT;
-        int kparts = 1;
-        if (dq_split_shape(bp.nq, heads, batch) && bp.dq_ld % 4 == 0 && bp.dq_sb % 4 == 0 && tg_aligned16(bp.dq)) {
-            kparts = (int)((6L * tg_device_cus()) / wgs);
-            if (kparts > DQ_SPLIT_MAX) kparts = DQ_SPLIT_MAX;
-            if (kparts > ntile / 16) kparts = (int)(ntile / 16);               // at least 16 key tiles per range
-            if (kparts < 2) kparts = 1;
-        }
-        P[i].pp.kparts = kparts;
-        P[i].pp.dq_part = (float*)(((uintptr_t)(P[i].cnt + P[i].ncnt + (long)batch * heads) + 15) & ~(uintptr_t)15);
-        hipLaunchKernelGGL(attn_bwd_dq2_kernel, dim3((unsigned)(wgs * kparts)), dim3(256), 0, stream, P[i].pp);
-        if (kparts > 1) {
-            const long n4 = (long)batch * bp.nq * heads * HD / 4;
-            hipLaunchKernelGGL(attn_bwd_dq_join_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, P[i].pp);
-        }
+        const AttnBwdProblemPlan& pr = pl.pr[i];
+        if (pr.one_kernel) continue;
+        hipLaunchKernelGGL(attn_bwd_dkdv7_kernel, dim3(pr.wgs_k), dim3(512), 0, stream, P[i].pp);
+        P[i].pp.kparts = pr.kparts;
+        P[i].pp.dq_part = P[i].dq_part;
+        hipLaunchKernelGGL(attn_bwd_dq2_kernel, dim3(pr.dq_grid), dim3(256), 0, stream, P[i].pp);
+        if (pr.join_grid) hipLaunchKernelGGL(attn_bwd_dq_join_kernel, dim3(pr.join_grid), dim3(256), 0, stream, P[i].pp);
         TG_LAUNCH_CHECK("tg_attention_bwd");
     }
     return TG_OK;
 }
+
