@@ -744,6 +744,34 @@ int tg_relu_maxpool2_cl(const void* x, int F, int H, int W, int C, void* y, hipS
 long tg_lpips_head_ws_doubles(int F, int H, int W);
 int tg_lpips_head(const void* fa, const void* fb, const float* w, int F, int H, int W, int C, int relu_on_load, double* ws, double* out, hipStream_t stream);
 
+/* The T5 text encoder (csrc/t5.hip; host side: tokensgen_amd/t5.py): transformers' T5EncoderModel in the CogVideoX-5b text_encoder configuration
+ * (gated-gelu feed-forward, d_kv 64, no biases, no mask) as the reference calls it in _get_t5_prompt_embeds (pipeline_cogvideox_mp_fifo.py:365-405,
+ * pipeline_cogvideox_t2to.py:313-353) and compute_prompt_embeddings (train_cogvideo_to2v.py:952-980).  Every projection (q | k | v fused, o, wi_0 | wi_1 fused, wo) is
+ * tg_gemm_bf16 with bias == NULL; these four exports are the rest of a block.
+ * tg_rmsnorm: y[r][c] = bf16( w[c] * bf16( x[r][c] * rsqrt( mean_c(x[r][c]^2) + eps ) ) ) — T5LayerNorm: no mean subtraction, no bias, the sum of squares in fp32, the
+ *   normalised value rounded to bf16 BEFORE the multiplication by the bf16 weight as the library does for half-precision weights.  x [rows][D] with row stride ldx, y
+ *   with ldy, D % 64 == 0; x, w, y 16-byte aligned, ldx and ldy multiples of 8.  A row's result depends on that row alone (one wave per row, fixed summation order).  A row of zeros gives zeros.
+ * tg_t5_attention: out[b][i][h * 64 + :] = sum_j P[i][j] v[b][j][h * 64 + :], P = bf16( softmax_j( fp32( q[b][i][h*64+:] . k[b][j][h*64+:] ) + bias_by_distance[h][j - i + S - 1] ) )
+ *   — T5Attention.forward without a mask: NO 1/sqrt(d) scale, every one of the S positions (padding included) attends and is attended to, softmax in fp32 and P rounded
+ *   to bf16 (`.type_as(scores)`).  q, k, v: three pointers into the fused QKV GEMM output (or anywhere else), element [b][s][h * 64 + d] at b * stride_b + s * ld + h * 64 + d;
+ *   bias_by_distance: fp32 [H][2 S - 1], relative_attention_bias.weight[bucket(j - i)][h] laid out by distance (the host builds it once per S: the library's float32
+ *   `log` decides the bucket boundaries); out: bf16 [B][S][H * 64], contiguous.  Head dimension 64 only; 1 <= S <= 512 (one head's K and V stay in LDS and the softmax
+ *   is exact over the resident row, no on-line rescaling), TG_ERR_SHAPE otherwise.  q, k, v 16-byte aligned, ld and stride_b multiples of 8.
+ * tg_gated_gelu: out[r][c] = bf16( gelu_tanh(h[r][c]) * h[r][F + c] ), c < F — T5DenseGatedActDense (`gated-gelu` = gelu_new, the tanh form) on the [rows][2 F] output
+ *   of one GEMM over the concatenated wi_0 | wi_1 weight; gelu_tanh is the fp32 function of tg_act mode 2 and of TG_EPI_BIAS_GELU.  F % 8 == 0; h, out 16-byte aligned,
+ *   ldh, ldo multiples of 8.
+ * tg_residual_add: out[i] = bf16(x[i] + y[i]), n % 8 == 0, 16-byte aligned, out may be x or y — hidden_states + dropout(layer_output) of T5LayerSelfAttention / T5LayerFF.
+ *   A separate pass, not TG_EPI_BIAS_GATE_RES with a gate of 1, by measurement (tools/t5_residual_probe.py, profiles/t5_residual_probe.json: 24 layers' o / wo
+ *   projections at [1 | 3] x 226 rows, same process, alternating): GEMM + this pass 1.58 / 3.68 ms (K = 4096 / 10240, batch 1) and 1.58 / 3.66 ms (batch 3) against
+ *   1.63 / 3.72 and 1.59 / 3.66 ms for the epilogue — a GEMM launch at these row counts takes 65 - 150 us to stream its 34 - 84 MB of weights and the 1.9 MB pass disappears beside it.  The
+ *   separate pass also keeps the library's rounding (the projection rounded to bf16, then the sum; the 128 x 128 kernel's epilogue adds the fp32 accumulator) and
+ *   needs no gate table. */
+int tg_rmsnorm(const void* x, long ldx, const void* w, void* y, long ldy, long rows, int D, float eps, hipStream_t stream);
+int tg_t5_attention(const void* q, const void* k, const void* v, long ld, long stride_b, const float* bias_by_distance, void* out, int B, int S, int H,
+                    hipStream_t stream);
+int tg_gated_gelu(const void* h, long ldh, void* out, long ldo, long rows, int F, hipStream_t stream);
+int tg_residual_add(const void* x, const void* y, void* out, long n, hipStream_t stream);
+
 /* Dispatch overrides for the cross-check tests — NOT part of the operator surface.  The library reads no environment variable and keeps no other
  * process-wide state: the defaults are the shipped path, and these knobs only choose between two PRODUCT kernels of the same operator (each pair is held
  * bitwise or to rounding against each other by tests/).  Knobs: TG_ATTN_PP_MIN_WG (1024: workgroups from which the 8-wave attention kernel is used),

@@ -1051,3 +1051,51 @@ def lpips_head(fa, fb, w, relu_on_load=False):
     out = torch.empty(F, dtype=torch.float64, device=fa.device)
     L.check(_launch("lpips_head", lib.tg_lpips_head, _p(fa), _p(fb), _p(w), F, H, W, Cn, int(bool(relu_on_load)), _p(ws), _p(out), _stream()), "tg_lpips_head")
     return out
+
+
+def rmsnorm(x, weight, out, eps=1e-6):
+    """tg_rmsnorm (T5LayerNorm): out = weight * bf16(x * rsqrt(mean(x^2) + eps)) over the last dimension; x, out [.., D] views with contiguous rows of one row
+    stride (D % 64 == 0), weight [D]."""
+    _chk(x, "x"); _chk(weight, "weight"); _chk(out, "out")
+    D = x.shape[-1]
+    x2, o2 = x.reshape(-1, D) if x.dim() != 2 else x, out.reshape(-1, D) if out.dim() != 2 else out
+    if x2.data_ptr() != x.data_ptr() or o2.data_ptr() != out.data_ptr() or x2.shape != o2.shape or tuple(weight.shape) != (D,) or not weight.is_contiguous():
+        raise ValueError(f"rmsnorm: x{tuple(x.shape)} and out{tuple(out.shape)} must be views with one row stride over [rows, D], weight [D]")
+    L.check(_launch("rmsnorm", L.load().tg_rmsnorm, _p(x2), x2.stride(0), _p(weight), _p(o2), o2.stride(0), x2.shape[0], D, float(eps), _stream()), "tg_rmsnorm")
+    return out
+
+
+def t5_attention(qkv, bias_by_distance, out, heads):
+    """tg_t5_attention on the fused projection: qkv [B, S, 3 * heads * 64] (q | k | v along the last dimension, a view with row / batch strides allowed),
+    bias_by_distance fp32 [heads, 2 S - 1], out contiguous [B, S, heads * 64]: softmax_fp32(q k^T + bias) v per head, unscaled and unmasked.  1 <= S <= 512."""
+    _chk(qkv, "qkv"); _chk(bias_by_distance, "bias_by_distance", torch.float32); _chk(out, "out")
+    if qkv.dim() != 3 or qkv.shape[2] != 3 * heads * 64:
+        raise ValueError(f"t5_attention: qkv must be [B, S, {3 * heads * 64}], got {tuple(qkv.shape)}")
+    B, S, _ = qkv.shape
+    inner = heads * 64
+    if tuple(out.shape) != (B, S, inner) or not out.is_contiguous() or tuple(bias_by_distance.shape) != (heads, 2 * S - 1) or not bias_by_distance.is_contiguous():
+        raise ValueError(f"t5_attention: out must be contiguous {(B, S, inner)} and bias_by_distance contiguous {(heads, 2 * S - 1)}, got {tuple(out.shape)} and "
+                         f"{tuple(bias_by_distance.shape)}")
+    p = qkv.data_ptr()
+    L.check(_launch("t5_attention", L.load().tg_t5_attention, p, p + 2 * inner, p + 4 * inner, qkv.stride(1), qkv.stride(0), _p(bias_by_distance), _p(out), B, S, heads,
+                    _stream()), "tg_t5_attention")
+    return out
+
+
+def gated_gelu(h, out):
+    """tg_gated_gelu: out [.., F] = bf16(gelu_tanh(h[.., :F]) * h[.., F:]), h [.., 2 F] the output of one GEMM over wi_0 | wi_1; both contiguous."""
+    _chk(h, "h"); _chk(out, "out")
+    F = out.shape[-1]
+    if h.shape[-1] != 2 * F or h.shape[:-1] != out.shape[:-1] or not h.is_contiguous() or not out.is_contiguous():
+        raise ValueError(f"gated_gelu: expected contiguous h [.., 2 F] and out [.., F], got {tuple(h.shape)} and {tuple(out.shape)}")
+    L.check(_launch("gated_gelu", L.load().tg_gated_gelu, _p(h), 2 * F, _p(out), F, out.numel() // max(F, 1), F, _stream()), "tg_gated_gelu")
+    return out
+
+
+def residual_add(x, y, out):
+    """tg_residual_add: out = bf16(x + y), three contiguous tensors of one shape (out may be x)."""
+    _chk(x, "x"); _chk(y, "y"); _chk(out, "out")
+    if not (x.shape == y.shape == out.shape) or not (x.is_contiguous() and y.is_contiguous() and out.is_contiguous()):
+        raise ValueError(f"residual_add: expected three contiguous tensors of one shape, got {tuple(x.shape)}, {tuple(y.shape)}, {tuple(out.shape)}")
+    L.check(_launch("residual_add", L.load().tg_residual_add, _p(x), _p(y), _p(out), x.numel(), _stream()), "tg_residual_add")
+    return out

@@ -81,6 +81,10 @@ PROTOTYPES = {
     "tg_relu_cl": [_vp, _l, _vp],
     "tg_relu_maxpool2_cl": [_vp, _i, _i, _i, _i, _vp, _vp],
     "tg_lpips_head": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp],
+    "tg_rmsnorm": [_vp, _l, _vp, _vp, _l, _l, _i, _f, _vp],
+    "tg_t5_attention": [_vp, _vp, _vp, _l, _l, _vp, _vp, _i, _i, _i, _vp],
+    "tg_gated_gelu": [_vp, _l, _vp, _l, _l, _i, _vp],
+    "tg_residual_add": [_vp, _vp, _vp, _l, _vp],
     "tg_conv3d_cl": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _l, _i, _i, _i, _vp, _vp, _vp, _vp],
     "tg_conv3d_up2_subpixel": [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _l, _i, _vp, _vp, _vp],
     "tg_groupnorm_finalize": [_vp, _l, _i, _f, _vp, _vp],

@@ -1,10 +1,11 @@
 """MPFIFOVideoIPAdapterCogVideoXPipeline — host mirror of the parts of longvgen/pipeline/pipeline_cogvideox_mp_fifo.py that
 are on the hot path: the 52-step base stage on chunk 0 that seeds the FIFO queue (:1186-1307),
 `prepare_latents` (:650-674), the RoPE helpers (:769-813), `preprare_for_fifo` (sic, :1491-1514) and `decode_latents`
-(:676-684).  Prompt encoding (T5) and the condensed-token encoder (Resampler) are upstream of the path: pass
-`prompt_embeds` / `negative_prompt_embeds` tensors, and either `image_embeddings` (as the reference's own `image_embeddings is not
+(:676-684).  Prompt encoding (:365-486) runs inside the call when a `text_encoder` (tokensgen_amd.t5.T5EncoderModel) and a `tokenizer` are attached:
+`prompt=` / `negative_prompt=` are then encoded by tokensgen_amd.t5.encode_prompt; without them pass `prompt_embeds` / `negative_prompt_embeds` tensors.  The
+condensed tokens come from either `image_embeddings` (as the reference's own `image_embeddings is not
 None` branch does, :611-616) or the source video as `frames` (:1151-1164, encoded by `vae_encode_image`; tokensgen_amd.video_io.prepare_video
-makes that tensor from decoded uint8 frames); passing a raw prompt raises NotImplementedError.
+makes that tensor from decoded uint8 frames); passing a raw prompt with no encoder attached raises NotImplementedError.
 """
 import os
 from types import SimpleNamespace
@@ -21,8 +22,12 @@ from .fifo import BF16
 
 
 class MPFIFOVideoIPAdapterCogVideoXPipeline:
-    def __init__(self, transformer, scheduler, vae=None, resampler_config=None, device=None, resampler=None):
+    text_encoder = None            # tokensgen_amd.t5.T5EncoderModel; with `tokenizer` attached too, __call__ accepts `prompt=`
+    tokenizer = None               # the caller's transformers.T5Tokenizer (or any object with its call interface)
+
+    def __init__(self, transformer, scheduler, vae=None, resampler_config=None, device=None, resampler=None, text_encoder=None, tokenizer=None):
         self.transformer, self.scheduler, self.vae = transformer, scheduler, vae
+        self.text_encoder, self.tokenizer = text_encoder, tokenizer
         self._resampler = resampler
         self.device = torch.device(device) if device is not None else transformer.device
         self.vae_scale_factor_spatial = 2 ** (len(vae.config.block_out_channels) - 1) if vae is not None else 8
@@ -33,11 +38,11 @@ class MPFIFOVideoIPAdapterCogVideoXPipeline:
         self._guidance_scale = 6.0
 
     @classmethod
-    def from_pretrained(cls, path, transformer=None, resampler=None, torch_dtype=BF16, device="cuda", **unused):
+    def from_pretrained(cls, path, transformer=None, resampler=None, torch_dtype=BF16, device="cuda", text_encoder=None, tokenizer=None, **unused):
         """DiffusionPipeline.from_pretrained as the entry script calls it (infer_cogvideo_mp_fifo.py:122-127, 171-176): the transformer and the
         resampler are handed in; the VAE comes from `<path>/vae`, the scheduler configuration from `<path>/scheduler/scheduler_config.json`.
-        The T5 tokenizer / text encoder are NOT loaded: prompt encoding stays on the reference side and `prompt_embeds`
-        are passed in."""
+        The T5 tokenizer / text encoder are NOT loaded here: hand them in (`text_encoder=tokensgen_amd.t5.T5EncoderModel.from_pretrained(path)`,
+        `tokenizer=` the caller's T5Tokenizer) to have `prompt=` encoded inside the call, or pass `prompt_embeds`."""
         from .scheduler import CogVideoXDPMScheduler
         from .transformer import CogVideoXTransformer3DModel
         from .vae import AutoencoderKLCogVideoX
@@ -46,7 +51,7 @@ class MPFIFOVideoIPAdapterCogVideoXPipeline:
             transformer = CogVideoXTransformer3DModel.from_pretrained(path, subfolder="transformer", torch_dtype=torch_dtype, device=dev)
         vae = AutoencoderKLCogVideoX.from_pretrained(path, subfolder="vae", device=dev) if os.path.isdir(os.path.join(path, "vae")) else None
         sched = CogVideoXDPMScheduler.from_config(os.path.join(path, "scheduler", "scheduler_config.json"))
-        return cls(transformer, sched, vae=vae, resampler=resampler, device=dev)
+        return cls(transformer, sched, vae=vae, resampler=resampler, device=dev, text_encoder=text_encoder, tokenizer=tokenizer)
 
     def to(self, device=None, *unused, **kw):
         """`pipe.to(device)`: the modules already live on the device they were built on; a different device moves them."""
@@ -57,6 +62,8 @@ class MPFIFOVideoIPAdapterCogVideoXPipeline:
                 self.vae.to(self.device)
             if self._resampler is not None:
                 self._resampler.to(self.device)
+            if self.text_encoder is not None:
+                self.text_encoder.to(self.device)
         return self
 
     @property
@@ -167,7 +174,8 @@ class MPFIFOVideoIPAdapterCogVideoXPipeline:
                  height=480, width=720, num_frames_per_chunk=49, num_chunks=1, num_inference_steps=52, guidance_scale=6.0,
                  video_ipadapter_scale=None, video_ipadapter_start_frame_idx=1000, latents=None, generator=None, step_noise=None,
                  sampling_params=None, output_type="latent", return_dict=False, cfg_parallel=None, use_separate_guidance=False,
-                 guidance_scale_img=None, use_dynamic_cfg=False, uncond_image_embeddings=None, vip_generator=None, **unused):
+                 guidance_scale_img=None, use_dynamic_cfg=False, uncond_image_embeddings=None, vip_generator=None, negative_prompt=None,
+                 max_sequence_length=226, **unused):
         """Base stage (:837-1344): `num_inference_steps` scalar-timestep CFG steps on chunk 0, harvesting
         `latents[:, max(0, 12-i)]` (and the matching x0) into the FIFO seed lists before every step (:1190-1194).
         step_noise: optional callable i -> [nf,2,C,h,w] bf16 (default: seeded device generator).  With a CogVideoXDDIMScheduler the steps are
@@ -180,10 +188,18 @@ class MPFIFOVideoIPAdapterCogVideoXPipeline:
         frames (:1151-1164): the source video [1, F, 3, H, W] in [-1, 1] (tokensgen_amd.video_io.prepare_video); used when image_embeddings is None:
         `vae_encode_image(frames)` with this call's num_frames_per_chunk, video_ipadapter_start_frame_idx, use_separate_guidance and CFG flag.  vip_generator: the
         generator of the posterior draw of that encode (the reference draws it from the global RNG, separately from `generator`; None does the same).  With a process
-        group up that encode is COLLECTIVE (its chunks are sharded over the ranks and gathered): every rank must then make this call with the same frames."""
-        if prompt is not None:
-            raise NotImplementedError("T5 prompt encoding is upstream of the hot path: pass prompt_embeds / negative_prompt_embeds")
+        group up that encode is COLLECTIVE (its chunks are sharded over the ranks and gathered): every rank must then make this call with the same frames.
+        prompt / negative_prompt / max_sequence_length (:1015-1029): one prompt (a str or a list of one), encoded here by the attached text_encoder + tokenizer
+        (tokensgen_amd.t5.encode_prompt; the negative prompt defaults to ""); under a process group every rank encodes it itself (deterministic: no collective)."""
         do_cfg = guidance_scale > 1.0                                                               # :1012
+        if prompt is not None:
+            if self.text_encoder is None or self.tokenizer is None:
+                raise NotImplementedError("T5 prompt encoding is upstream of the hot path: pass prompt_embeds / negative_prompt_embeds")
+            if not isinstance(prompt, str) and len(prompt) != 1:
+                raise NotImplementedError("one prompt per call (the base stage runs one clip)")
+            from .t5 import encode_prompt
+            prompt_embeds, negative_prompt_embeds = encode_prompt(self.tokenizer, self.text_encoder, prompt, negative_prompt, do_cfg, 1, prompt_embeds,
+                                                                  negative_prompt_embeds, max_sequence_length, device=self.device, dtype=BF16)
         if prompt_embeds is None or (do_cfg and negative_prompt_embeds is None):
             raise ValueError("prompt_embeds (and, with guidance_scale > 1, negative_prompt_embeds) are required")
         dev = self.device

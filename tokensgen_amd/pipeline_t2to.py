@@ -4,7 +4,8 @@ Host mirror of the reference's `LongVGenCogVideoXPipeline` (longvgen/pipeline/pi
 a plain (no-vip) CogVideoX DiT with patch_size 1 over latents [1, num_chunks*4, 16, 8, 12], RoPE split 52/6/6 over
 integer grids (:543-564), classifier-free guidance with the optional cosine "dynamic" schedule (:852-855), the SDE
 DPM-solver++ loop with fp32 solver state (:845-870) and the de-normalise + PCA-inverse tail (:890-899) — every device op
-goes through libtokensgen_hip.so.  T5 prompt encoding is upstream of the path: pass prompt_embeds / negative_prompt_embeds.
+goes through libtokensgen_hip.so.  With a `text_encoder` (tokensgen_amd.t5.T5EncoderModel) and a `tokenizer` attached, `prompt=` / `negative_prompt=` are
+encoded inside the call (:313-434, tokensgen_amd.t5.encode_prompt); without them pass prompt_embeds / negative_prompt_embeds.
 """
 import math
 import os
@@ -31,8 +32,12 @@ def _load(x):
 
 
 class LongVGenCogVideoXPipeline:
-    def __init__(self, transformer, scheduler, device=None, **unused):
+    text_encoder = None            # tokensgen_amd.t5.T5EncoderModel; with `tokenizer` attached too, __call__ accepts `prompt=`
+    tokenizer = None               # the caller's transformers.T5Tokenizer (or any object with its call interface)
+
+    def __init__(self, transformer, scheduler, device=None, text_encoder=None, tokenizer=None, **unused):
         self.transformer = transformer
+        self.text_encoder, self.tokenizer = text_encoder, tokenizer
         self.scheduler = scheduler
         self.device = torch.device(device) if device is not None else transformer.device
         self._guidance_scale = 6.0
@@ -41,19 +46,23 @@ class LongVGenCogVideoXPipeline:
             raise ValueError("the T2To model is a plain CogVideoX DiT: do not call set_vip_layers on it")
 
     @classmethod
-    def from_pretrained(cls, path, transformer=None, torch_dtype=BF16, device="cuda", **unused):
+    def from_pretrained(cls, path, transformer=None, torch_dtype=BF16, device="cuda", text_encoder=None, tokenizer=None, **unused):
         """DiffusionPipeline.from_pretrained as the entry script calls it (infer_cogvideo_mp_fifo.py:225-229): the T2To transformer is handed
-        in, the scheduler configuration comes from `<path>/scheduler/scheduler_config.json`; T5 stays on the reference side."""
+        in, the scheduler configuration comes from `<path>/scheduler/scheduler_config.json`; the T5 encoder and tokenizer are not loaded here: hand them in
+        (`text_encoder=`, `tokenizer=`) to have `prompt=` encoded inside the call."""
         from .scheduler import CogVideoXDPMScheduler
         from .transformer import CogVideoXTransformer3DModel
         if transformer is None:
             transformer = CogVideoXTransformer3DModel.from_pretrained(path, subfolder="transformer", torch_dtype=torch_dtype, device=device)
-        return cls(transformer, CogVideoXDPMScheduler.from_config(os.path.join(path, "scheduler", "scheduler_config.json")))
+        return cls(transformer, CogVideoXDPMScheduler.from_config(os.path.join(path, "scheduler", "scheduler_config.json")), text_encoder=text_encoder,
+                   tokenizer=tokenizer)
 
     def to(self, device=None, *unused, **kw):
         if device is not None and not isinstance(device, torch.dtype) and torch.device(device) != self.device:
             self.device = torch.device(device)
             self.transformer.to(self.device)
+            if self.text_encoder is not None:
+                self.text_encoder.to(self.device)
         return self
 
     @property
@@ -92,7 +101,14 @@ class LongVGenCogVideoXPipeline:
         With a CogVideoXDDIMScheduler nothing is drawn after the initial latents and step_noise is never called.
         cfg_parallel: see tokensgen_amd/cfg_parallel.py (default: split the two CFG halves over ranks 0/1 when >= 2 ranks run)."""
         if prompt is not None or negative_prompt is not None:
-            raise NotImplementedError("T5 prompt encoding is upstream of the hot path: pass prompt_embeds and negative_prompt_embeds")
+            if self.text_encoder is None or self.tokenizer is None:
+                raise NotImplementedError("T5 prompt encoding is upstream of the hot path: pass prompt_embeds and negative_prompt_embeds")
+            if prompt is None and prompt_embeds is None:
+                raise ValueError("Provide either `prompt` or `prompt_embeds`. Cannot leave both `prompt` and `prompt_embeds` undefined.")
+            from .t5 import encode_prompt                    # under a process group every rank encodes the prompt itself (deterministic: no collective)
+            prompt_embeds, negative_prompt_embeds = encode_prompt(self.tokenizer, self.text_encoder, prompt, negative_prompt, guidance_scale > 1.0,
+                                                                  num_videos_per_prompt, prompt_embeds, negative_prompt_embeds, max_sequence_length,
+                                                                  device=self.device, dtype=BF16)
         if prompt_embeds is None:
             raise ValueError("Provide either `prompt` or `prompt_embeds`. Cannot leave both `prompt` and `prompt_embeds` undefined.")
         if num_frames_per_chunk > 4:
