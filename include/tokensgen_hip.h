@@ -535,6 +535,26 @@ int tg_adamw8bit_step(void* param, float* grad, uint8_t* state1, uint8_t* state2
                       const float* qmap1, const float* qmap2, const tg_adamw8bit_row* rows, int nrows, long nblocks, int block_size, int step,
                       float lr, float beta1, float beta2, float eps, float weight_decay, const float* clip_coef, int zero_grad, hipStream_t stream);
 
+/* Stochastic bf16 rounding of the parameter write (NOT in the reference: torch AdamW on bf16 parameters rounds to nearest even, and so do the two
+ * entry points above).  tg_adamw_step_sr / tg_adamw8bit_step_sr replace tg_adamw_step / tg_adamw8bit_step: the same arguments, the same
+ * fp32 arithmetic and the same moments, but the fp32 result x is written as one of its two bf16 neighbours with E[bf16(x)] = x, so an update
+ * smaller than half a bf16 ulp accumulates in expectation instead of being rounded away.  No extra state.
+ *   random bits: Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85), a pure function of (seed, step, arena
+ *     element index i): key = (seed & 0xffffffff, seed >> 32), counter = (g & 0xffffffff, g >> 32, step, 0) with g = i >> 3, W = philox(counter, key),
+ *     j = i & 7, r16 = (W[j >> 1] >> (16 * (j & 1))) & 0xffff.  One call serves 8 consecutive elements; launch geometry, pointers, rank and stream
+ *     never enter, so a resumed run (same step) and every data-parallel rank (same seed) draw the same bits.
+ *   rounding, u = bits of x: exponent field of u all ones (NaN, +-Inf) -> the round-to-nearest conversion of the entry points above; else s = u + r16,
+ *     and s = u if the exponent field of s is all ones (a finite x never becomes Inf); result = s >> 16.  A bf16-exact x is unchanged; the magnitude
+ *     rounds away from zero with probability low16(u) / 65536, for either sign.
+ * tg_adamw_step_sr: elem0 = arena index of param[0] (the optimizer steps an arena in two segments), a multiple of 8; all four arenas 16-byte
+ * aligned; n need not be a multiple of 8.  tg_adamw8bit_step_sr: param is the arena's first element, the rows' offsets are the arena indices. */
+int tg_adamw_step_sr(void* param, float* grad, float* exp_avg, float* exp_avg_sq, long n, int step, float lr, float beta1, float beta2, float eps,
+                     float weight_decay, const float* clip_coef, int zero_grad, long elem0, unsigned long long seed, hipStream_t stream);
+int tg_adamw8bit_step_sr(void* param, float* grad, uint8_t* state1, uint8_t* state2, float* absmax1, float* absmax2, float* small_m, float* small_v,
+                         const float* qmap1, const float* qmap2, const tg_adamw8bit_row* rows, int nrows, long nblocks, int block_size, int step,
+                         float lr, float beta1, float beta2, float eps, float weight_decay, const float* clip_coef, int zero_grad,
+                         unsigned long long seed, hipStream_t stream);
+
 /* Prodigy (the yaml's `optimizer: prodigy`; train_cogvideo_to2v.py:1109-1132, train_cogvideo_t2to.py get_optimizer; the algorithm is prodigyopt 1.0
  * Prodigy.step restated: DESIGN §8) over a whole arena: ONE step = three launches on `stream`, no host synchronisation.
  *   per element: exp_avg / exp_avg_sq / s / delta fp32, p0 bf16 (the start values); the parameter is never updated in place: delta = x - x0 is kept

@@ -797,10 +797,48 @@ __global__ __launch_bounds__(OPT_BLOCK) void prodigy_update_kernel(bf16_t* __res
     }
 }
 
+// Stochastic bf16 rounding of the parameter write (header: tg_adamw_step_sr; not in the reference).  Philox4x32-10 (Salmon et al., SC'11)
+// in plain integer arithmetic: the random bits of an element are a function of (seed, step, arena index) alone, so launch geometry, the two-segment
+// launch of AdamW.step and the rank never enter them.  One call serves the 8 consecutive elements of arena group g = index >> 3.
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&w)[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
+}
+struct SrKey {
+    uint32_t k0, k1, step;                                     // key = the seed's two halves; the step is counter word 2
+};
+__device__ __forceinline__ void sr_group_bits(const SrKey& key, long group, uint32_t (&w)[4]) {
+    philox4x32_10((uint32_t)group, (uint32_t)((unsigned long long)group >> 32), key.step, 0u, key.k0, key.k1, w);
+}
+// the 16 random bits of element j (0..7) of a group; selects, no indexed register array (j is a constant wherever EPL == 8)
+__device__ __forceinline__ uint32_t sr_r16(const uint32_t (&w)[4], int j) {
+    const int h = j >> 1;
+    const uint32_t ww = h == 0 ? w[0] : h == 1 ? w[1] : h == 2 ? w[2] : w[3];
+    return (ww >> (16 * (j & 1))) & 0xffffu;
+}
+// x to one of its two bf16 neighbours, the magnitude away from zero with probability low16(bits) / 65536: E[result] = x.  A bf16-exact x is
+// unchanged; NaN / Inf take the round-to-nearest conversion; a carry into the all-ones exponent is dropped (a finite x never becomes Inf).
+__device__ __forceinline__ bf16_t f32_to_bf16_sr(float x, uint32_t r16) {
+    const uint32_t u = __float_as_uint(x);
+    if ((u & 0x7f800000u) == 0x7f800000u) return f32_to_bf16(x);
+    uint32_t s = u + r16;
+    if ((s & 0x7f800000u) == 0x7f800000u) s = u;
+    return (bf16_t)(s >> 16);
+}
+
 // Block-wise 8-bit AdamW (header: tg_adamw8bit_step).  One 256-lane workgroup per quantisation block of OPT_BLOCK * EPL elements, EPL contiguous
 // elements per lane (16-byte bf16 / 2 x 16-byte fp32 / 8-byte code accesses at EPL = 8).  The workgroup finds its tensor by a binary search over the
 // table's first_block (the same index in every lane: scalar loads).  A lane whose chunk starts inside the tensor reads its whole chunk: the chunk ends
 // inside the tensor's 64-element-aligned arena slot, so the tail lane's extra elements are padding that is read, masked out and never written.
+// SR (tg_adamw8bit_step_sr): the parameter write rounds stochastically with the bits of arena index a + k; a lane's chunk lies inside one group of 8
+// (a is a multiple of EPL), so with EPL < 8 the 8 / EPL lanes of a group each compute the group's Philox and pick their own halves.  SR = false
+// compiles to the code without it (sr is never read).
 template <int EPL>
 struct Chunk {
     typedef __attribute__((ext_vector_type(EPL))) float f;
@@ -818,12 +856,12 @@ __device__ __forceinline__ int quantize_nearest(const float* q, float x) {
     return (q[j + 1] - x) < (x - q[j]) ? j + 1 : j;
 }
 
-template <int EPL>
+template <int EPL, bool SR>
 __global__ __launch_bounds__(OPT_BLOCK) void adamw8bit_kernel(bf16_t* __restrict__ p, float* __restrict__ g, uint8_t* __restrict__ s1, uint8_t* __restrict__ s2,
                                                               float* __restrict__ amax1, float* __restrict__ amax2, float* __restrict__ sm, float* __restrict__ sv,
                                                               const float* __restrict__ qmap1, const float* __restrict__ qmap2,
                                                               const tg_adamw8bit_row* __restrict__ rows, int nrows, float lr, float b1, float b2, float eps, float wd,
-                                                              float bc1, float bc2_sqrt, const float* __restrict__ clip, int zero_grad) {
+                                                              float bc1, float bc2_sqrt, const float* __restrict__ clip, int zero_grad, SrKey sr) {
     typedef typename Chunk<EPL>::f fv;
     typedef typename Chunk<EPL>::h hv;
     typedef typename Chunk<EPL>::b bv;
@@ -914,17 +952,83 @@ __global__ __launch_bounds__(OPT_BLOCK) void adamw8bit_kernel(bf16_t* __restrict
             for (int k = 0; k < nv; ++k) { s1[a + k] = c1[k]; s2[a + k] = c2[k]; }
         }
     }
+    uint32_t w[4] = {};
+    if constexpr (SR) sr_group_bits(sr, a >> 3, w);
+    const int j0 = EPL == 8 ? 0 : (int)(a & 7);                // EPL == 8: a is a multiple of 8 (the 16-byte accesses above)
+    auto to_bf16 = [&](int k) -> bf16_t {
+        if constexpr (SR) return f32_to_bf16_sr(pf[k], sr_r16(w, j0 + k));
+        else return f32_to_bf16(pf[k]);
+    };
     if (nv == EPL) {
         hv ph;
         fv z = {};
 #pragma unroll
-        for (int k = 0; k < EPL; ++k) ph[k] = f32_to_bf16(pf[k]);
+        for (int k = 0; k < EPL; ++k) ph[k] = to_bf16(k);
         *reinterpret_cast<hv*>(p + a) = ph;
         if (zero_grad) *reinterpret_cast<fv*>(g + a) = z;
     } else {
         for (int k = 0; k < nv; ++k) {
-            p[a + k] = f32_to_bf16(pf[k]);
+            p[a + k] = to_bf16(k);
             if (zero_grad) g[a + k] = 0.f;
+        }
+    }
+}
+
+// tg_adamw_step_sr: adamw_kernel's arithmetic with the stochastic parameter write.  A lane owns the 8 consecutive elements of one arena group (one
+// Philox call per group; 16-byte bf16 / 2 x 16-byte fp32 accesses); elem0 = arena index of p[0], a multiple of 8, so group q of this segment is
+// arena group elem0 / 8 + q.  The last group of a segment whose n is no multiple of 8 is stepped element by element and writes nothing past n.
+__global__ __launch_bounds__(OPT_BLOCK) void adamw_sr_kernel(bf16_t* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long n,
+                                                             float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
+                                                             const float* __restrict__ clip, int zero_grad, long group0, SrKey sr) {
+    typedef Chunk<8>::f fv;
+    typedef Chunk<8>::h hv;
+    const float cs = clip ? *clip : 1.f;
+    const long groups = (n + 7) >> 3;
+    for (long q = (long)blockIdx.x * OPT_BLOCK + threadIdx.x; q < groups; q += (long)gridDim.x * OPT_BLOCK) {
+        const long i0 = q << 3;
+        const int nv = n - i0 < 8 ? (int)(n - i0) : 8;
+        float pf[8] = {}, gf[8] = {}, mf[8] = {}, vf[8] = {};
+        if (nv == 8) {
+            const hv ph = *reinterpret_cast<const hv*>(p + i0);
+            const fv gg = *reinterpret_cast<const fv*>(g + i0), mm = *reinterpret_cast<const fv*>(m + i0), vv = *reinterpret_cast<const fv*>(v + i0);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { pf[k] = bf16_to_f32(ph[k]); gf[k] = gg[k]; mf[k] = mm[k]; vf[k] = vv[k]; }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if (k < nv) { pf[k] = bf16_to_f32(p[i0 + k]); gf[k] = g[i0 + k]; mf[k] = m[i0 + k]; vf[k] = v[i0 + k]; }
+        }
+        uint32_t w[4];
+        sr_group_bits(sr, group0 + q, w);
+        bf16_t pb[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {                          // the adamw_kernel expression, term for term
+            const float gi = gf[k] * cs;
+            float pi = pf[k];
+            pi *= 1.f - lr * wd;
+            const float mi = b1 * mf[k] + (1.f - b1) * gi;
+            const float vi = b2 * vf[k] + (1.f - b2) * gi * gi;
+            mf[k] = mi; vf[k] = vi;
+            const float denom = sqrtf(vi) / bc2_sqrt + eps;
+            pi -= (lr / bc1) * (mi / denom);
+            pb[k] = f32_to_bf16_sr(pi, sr_r16(w, k));
+        }
+        if (nv == 8) {
+            hv ph;
+            fv mm, vv, z = {};
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { ph[k] = pb[k]; mm[k] = mf[k]; vv[k] = vf[k]; }
+            *reinterpret_cast<hv*>(p + i0) = ph;
+            *reinterpret_cast<fv*>(m + i0) = mm;
+            *reinterpret_cast<fv*>(v + i0) = vv;
+            if (zero_grad) *reinterpret_cast<fv*>(g + i0) = z;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if (k < nv) {
+                    p[i0 + k] = pb[k]; m[i0 + k] = mf[k]; v[i0 + k] = vf[k];
+                    if (zero_grad) g[i0 + k] = 0.f;
+                }
         }
     }
 }
@@ -987,6 +1091,21 @@ extern "C" int tg_adamw_step(void* param, float* grad, float* exp_avg, float* ex
     return TG_OK;
 }
 
+extern "C" int tg_adamw_step_sr(void* param, float* grad, float* exp_avg, float* exp_avg_sq, long n, int step, float lr, float beta1, float beta2, float eps,
+                                float weight_decay, const float* clip_coef, int zero_grad, long elem0, unsigned long long seed, hipStream_t stream) {
+    TG_REQUIRE(param && grad && exp_avg && exp_avg_sq, TG_ERR_ARG, "tg_adamw_step_sr: null pointer");
+    TG_REQUIRE(n > 0 && step >= 1, TG_ERR_SHAPE, "tg_adamw_step_sr: n and step must be positive");
+    TG_REQUIRE(elem0 >= 0 && elem0 % 8 == 0, TG_ERR_SHAPE, "tg_adamw_step_sr: elem0 %ld must be a non-negative multiple of 8 (one Philox call per 8 arena elements)", elem0);
+    TG_REQUIRE(tg_aligned16(param) && tg_aligned16(grad) && tg_aligned16(exp_avg) && tg_aligned16(exp_avg_sq), TG_ERR_ALIGN,
+               "tg_adamw_step_sr: arenas must be 16-byte aligned");
+    const float bc1 = 1.f - powf(beta1, (float)step), bc2s = sqrtf(1.f - powf(beta2, (float)step));
+    const SrKey sr = {(uint32_t)(seed & 0xffffffffull), (uint32_t)(seed >> 32), (uint32_t)step};
+    hipLaunchKernelGGL(adamw_sr_kernel, dim3(opt_blocks((n + 7) / 8)), dim3(OPT_BLOCK), 0, stream, (bf16_t*)param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2,
+                       eps, weight_decay, bc1, bc2s, clip_coef, zero_grad, elem0 / 8, sr);
+    TG_LAUNCH_CHECK("tg_adamw_step_sr");
+    return TG_OK;
+}
+
 extern "C" long tg_prodigy_ws_doubles(void) { return 2L * OPT_MAX_BLOCKS; }
 
 extern "C" int tg_prodigy_step(void* param, float* grad, float* exp_avg, float* exp_avg_sq, float* s, float* delta, const void* p0, double* state, double* ws,
@@ -1024,28 +1143,50 @@ extern "C" int tg_prodigy_step(void* param, float* grad, float* exp_avg, float* 
     return TG_OK;
 }
 
+namespace {
+// tg_adamw8bit_step / tg_adamw8bit_step_sr: the checks and the launch; `sr` NULL = round to nearest (the kernel instantiation without the generator)
+int adamw8bit_launch(const char* who, void* param, float* grad, uint8_t* state1, uint8_t* state2, float* absmax1, float* absmax2, float* small_m, float* small_v,
+                     const float* qmap1, const float* qmap2, const tg_adamw8bit_row* rows, int nrows, long nblocks, int block_size, int step, float lr,
+                     float beta1, float beta2, float eps, float weight_decay, const float* clip_coef, int zero_grad, const SrKey* sr, hipStream_t stream) {
+    TG_REQUIRE(param && grad && state1 && state2 && absmax1 && absmax2 && small_m && small_v && qmap1 && qmap2 && rows, TG_ERR_ARG, "%s: null pointer", who);
+    TG_REQUIRE(nrows > 0 && nblocks > 0 && step >= 1, TG_ERR_SHAPE, "%s: nrows, nblocks and step must be positive", who);
+    TG_REQUIRE(nblocks < (1L << 31), TG_ERR_SHAPE, "%s: %ld workgroups", who, nblocks);
+    TG_REQUIRE(block_size == OPT_BLOCK || block_size == 2 * OPT_BLOCK || block_size == 4 * OPT_BLOCK || block_size == 8 * OPT_BLOCK, TG_ERR_SHAPE,
+               "%s: block_size %d not in {256, 512, 1024, 2048}", who, block_size);
+    TG_REQUIRE(tg_aligned16(param) && tg_aligned16(grad) && tg_aligned16(state1) && tg_aligned16(state2) && tg_aligned16(small_m) && tg_aligned16(small_v),
+               TG_ERR_ALIGN, "%s: arenas must be 16-byte aligned", who);
+    const float bc1 = 1.f - powf(beta1, (float)step), bc2s = sqrtf(1.f - powf(beta2, (float)step));
+    const SrKey key = sr ? *sr : SrKey{0u, 0u, 0u};
+#define TG_ADAM8_LAUNCH(E, SR)                                                                                                                              \
+    hipLaunchKernelGGL((adamw8bit_kernel<E, SR>), dim3((unsigned)nblocks), dim3(OPT_BLOCK), 0, stream, (bf16_t*)param, grad, state1, state2, absmax1, absmax2, \
+                       small_m, small_v, qmap1, qmap2, rows, nrows, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, clip_coef, zero_grad, key)
+#define TG_ADAM8_SWITCH(SR)                     \
+    switch (block_size / OPT_BLOCK) {           \
+        case 1: TG_ADAM8_LAUNCH(1, SR); break;  \
+        case 2: TG_ADAM8_LAUNCH(2, SR); break;  \
+        case 4: TG_ADAM8_LAUNCH(4, SR); break;  \
+        default: TG_ADAM8_LAUNCH(8, SR); break; \
+    }
+    if (sr) { TG_ADAM8_SWITCH(true) } else { TG_ADAM8_SWITCH(false) }
+#undef TG_ADAM8_SWITCH
+#undef TG_ADAM8_LAUNCH
+    TG_LAUNCH_CHECK(who);
+    return TG_OK;
+}
+}  // namespace
+
 extern "C" int tg_adamw8bit_step(void* param, float* grad, uint8_t* state1, uint8_t* state2, float* absmax1, float* absmax2, float* small_m, float* small_v,
                                  const float* qmap1, const float* qmap2, const tg_adamw8bit_row* rows, int nrows, long nblocks, int block_size, int step,
                                  float lr, float beta1, float beta2, float eps, float weight_decay, const float* clip_coef, int zero_grad, hipStream_t stream) {
-    TG_REQUIRE(param && grad && state1 && state2 && absmax1 && absmax2 && small_m && small_v && qmap1 && qmap2 && rows, TG_ERR_ARG,
-               "tg_adamw8bit_step: null pointer");
-    TG_REQUIRE(nrows > 0 && nblocks > 0 && step >= 1, TG_ERR_SHAPE, "tg_adamw8bit_step: nrows, nblocks and step must be positive");
-    TG_REQUIRE(nblocks < (1L << 31), TG_ERR_SHAPE, "tg_adamw8bit_step: %ld workgroups", nblocks);
-    TG_REQUIRE(block_size == OPT_BLOCK || block_size == 2 * OPT_BLOCK || block_size == 4 * OPT_BLOCK || block_size == 8 * OPT_BLOCK, TG_ERR_SHAPE,
-               "tg_adamw8bit_step: block_size %d not in {256, 512, 1024, 2048}", block_size);
-    TG_REQUIRE(tg_aligned16(param) && tg_aligned16(grad) && tg_aligned16(state1) && tg_aligned16(state2) && tg_aligned16(small_m) && tg_aligned16(small_v),
-               TG_ERR_ALIGN, "tg_adamw8bit_step: arenas must be 16-byte aligned");
-    const float bc1 = 1.f - powf(beta1, (float)step), bc2s = sqrtf(1.f - powf(beta2, (float)step));
-#define TG_ADAM8_LAUNCH(E)                                                                                                                          \
-    hipLaunchKernelGGL(adamw8bit_kernel<E>, dim3((unsigned)nblocks), dim3(OPT_BLOCK), 0, stream, (bf16_t*)param, grad, state1, state2, absmax1, absmax2, \
-                       small_m, small_v, qmap1, qmap2, rows, nrows, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, clip_coef, zero_grad)
-    switch (block_size / OPT_BLOCK) {
-        case 1: TG_ADAM8_LAUNCH(1); break;
-        case 2: TG_ADAM8_LAUNCH(2); break;
-        case 4: TG_ADAM8_LAUNCH(4); break;
-        default: TG_ADAM8_LAUNCH(8); break;
-    }
-#undef TG_ADAM8_LAUNCH
-    TG_LAUNCH_CHECK("tg_adamw8bit_step");
-    return TG_OK;
+    return adamw8bit_launch("tg_adamw8bit_step", param, grad, state1, state2, absmax1, absmax2, small_m, small_v, qmap1, qmap2, rows, nrows, nblocks, block_size,
+                            step, lr, beta1, beta2, eps, weight_decay, clip_coef, zero_grad, nullptr, stream);
+}
+
+extern "C" int tg_adamw8bit_step_sr(void* param, float* grad, uint8_t* state1, uint8_t* state2, float* absmax1, float* absmax2, float* small_m, float* small_v,
+                                    const float* qmap1, const float* qmap2, const tg_adamw8bit_row* rows, int nrows, long nblocks, int block_size, int step,
+                                    float lr, float beta1, float beta2, float eps, float weight_decay, const float* clip_coef, int zero_grad,
+                                    unsigned long long seed, hipStream_t stream) {
+    const SrKey sr = {(uint32_t)(seed & 0xffffffffull), (uint32_t)(seed >> 32), (uint32_t)step};
+    return adamw8bit_launch("tg_adamw8bit_step_sr", param, grad, state1, state2, absmax1, absmax2, small_m, small_v, qmap1, qmap2, rows, nrows, nblocks, block_size,
+                            step, lr, beta1, beta2, eps, weight_decay, clip_coef, zero_grad, &sr, stream);
 }

@@ -56,6 +56,8 @@ PROTOTYPES = {
     "tg_grad_clip_coef": [_vp, _l, _f, _vp, _vp, _vp],
     "tg_adamw_step": [_vp, _vp, _vp, _vp, _l, _i, _f, _f, _f, _f, _f, _vp, _i, _vp],
     "tg_adamw8bit_step": [_vp] * 11 + [_i, _l, _i, _i, _f, _f, _f, _f, _f, _vp, _i, _vp],
+    "tg_adamw_step_sr": [_vp, _vp, _vp, _vp, _l, _i, _f, _f, _f, _f, _f, _vp, _i, _l, C.c_ulonglong, _vp],
+    "tg_adamw8bit_step_sr": [_vp] * 11 + [_i, _l, _i, _i, _f, _f, _f, _f, _f, _vp, _i, C.c_ulonglong, _vp],
     "tg_prodigy_step": [_vp] * 9 + [_l, _l, _i] + [_d] * 9 + [_i, _i, _i, _vp, _i, _vp],
     "tg_lora_wgrad": [_vp, _l, _l, _vp, _l, _l, _i, _i, _i, _i, _vp, _l, _l, _f, _f, _vp, _vp],
     "tg_lora_merge": [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _f, _vp],

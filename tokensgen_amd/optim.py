@@ -117,16 +117,25 @@ class ParamArena:
         return [(n, int(self.offsets[n]), tuple(self.shapes[n])) for n in self.names]
 
 
+def _sr_seed(seed):
+    """The 64-bit Philox key of stochastic rounding from a yaml / argparse seed (None -> 0; negative values wrap)."""
+    return int(seed or 0) & 0xFFFFFFFFFFFFFFFF
+
+
 class AdamW:
     """torch.optim.AdamW semantics (decoupled weight decay) on a ParamArena, with the reference's gradient clipping folded in:
     `clip_elems` leading arena elements (the transformer's parameters, train_cogvideo_to2v.py:2014-2015) are clipped to `max_grad_norm` by their
-    global L2 norm; the rest (the Resampler) is stepped unclipped, as in the reference."""
+    global L2 norm; the rest (the Resampler) is stepped unclipped, as in the reference.  stochastic_round=True (not in the reference):
+    the bf16 parameter write rounds stochastically (tg_adamw_step_sr) with bits that depend on (sr_seed, step t, arena index) only; give every
+    data-parallel rank the same sr_seed."""
 
-    def __init__(self, arena, lr=2e-4, betas=(0.9, 0.95), eps=1e-8, weight_decay=1e-4, max_grad_norm=1.0, clip_elems=None):
+    def __init__(self, arena, lr=2e-4, betas=(0.9, 0.95), eps=1e-8, weight_decay=1e-4, max_grad_norm=1.0, clip_elems=None, stochastic_round=False,
+                 sr_seed=0):
         if arena.exp_avg is None:
             raise ValueError("AdamW needs a ParamArena with fp32 moments (moments=True); an arena built with moments=False is for AdamW8bit")
         self.arena, self.lr, self.betas, self.eps, self.wd, self.max_norm = arena, lr, betas, eps, weight_decay, max_grad_norm
         self.clip_elems = arena.numel if clip_elems is None else int(clip_elems)
+        self.stochastic_round, self.sr_seed = bool(stochastic_round), _sr_seed(sr_seed)
         self.t = 0
         dev = arena.param.device
         self._ws = torch.empty(L.load().tg_grad_norm_ws_floats(), dtype=torch.float32, device=dev)
@@ -145,22 +154,26 @@ class AdamW:
             clip_ptr = self.coef.data_ptr() + 4
         for lo, hi, cp in ((0, nc, clip_ptr), (nc, a.numel, None)):
             if hi > lo:
-                L.check(lib.tg_adamw_step(a.param.data_ptr() + 2 * lo, a.grad.data_ptr() + 4 * lo, a.exp_avg.data_ptr() + 4 * lo, a.exp_avg_sq.data_ptr() + 4 * lo,
-                                          hi - lo, self.t, float(lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.wd), cp,
-                                          1 if zero_grad else 0, st), "tg_adamw_step")
+                args = (a.param.data_ptr() + 2 * lo, a.grad.data_ptr() + 4 * lo, a.exp_avg.data_ptr() + 4 * lo, a.exp_avg_sq.data_ptr() + 4 * lo,
+                        hi - lo, self.t, float(lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.wd), cp, 1 if zero_grad else 0)
+                if self.stochastic_round:                                  # lo: the segment's absolute arena index (the random bits follow the element)
+                    L.check(lib.tg_adamw_step_sr(*args, lo, self.sr_seed, st), "tg_adamw_step_sr")
+                else:
+                    L.check(lib.tg_adamw_step(*args, st), "tg_adamw_step")
 
 
     # ---- checkpoint / resume (the reference: accelerator.save_state / load_state behind --resume_from_checkpoint, train_cogvideo_to2v.py:1690-1716,
     # 2030-2047).  Layout of the dict: {"t": optimizer steps taken (bias correction), "exp_avg" / "exp_avg_sq": the flat fp32 moment arenas,
     # "grad": the flat fp32 gradient arena (non-zero only in the middle of an accumulation window), "layout": ParamArena.layout(),
-    # "hyper": lr / betas / eps / weight_decay / max_grad_norm / clip_elems}.  Parameters are saved separately under the reference's names
+    # "hyper": lr / betas / eps / weight_decay / max_grad_norm / clip_elems / stochastic_round / sr_seed (with "t": a resume continues the same
+    # random stream; a checkpoint without the two keys loads as off)}.  Parameters are saved separately under the reference's names
     # (CogVideoXTransformer3DModel.save_vip_layers -> vip.pt, Resampler.save_pretrained).
     def state_dict(self):
         a = self.arena
         return {"t": int(self.t), "exp_avg": a.exp_avg.detach().cpu().clone(), "exp_avg_sq": a.exp_avg_sq.detach().cpu().clone(),
                 "grad": a.grad.detach().cpu().clone(), "layout": a.layout(),
                 "hyper": {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd, "max_grad_norm": self.max_norm,
-                          "clip_elems": self.clip_elems}}
+                          "clip_elems": self.clip_elems, "stochastic_round": self.stochastic_round, "sr_seed": self.sr_seed}}
 
     @torch.no_grad()
     def load_state_dict(self, sd):
@@ -179,6 +192,7 @@ class AdamW:
         h = sd.get("hyper", {})
         self.lr, self.betas, self.eps = h.get("lr", self.lr), tuple(h.get("betas", self.betas)), h.get("eps", self.eps)
         self.wd, self.max_norm, self.clip_elems = h.get("weight_decay", self.wd), h.get("max_grad_norm", self.max_norm), int(h.get("clip_elems", self.clip_elems))
+        self.stochastic_round, self.sr_seed = bool(h.get("stochastic_round", False)), _sr_seed(h.get("sr_seed", 0))
 
 
 def dynamic_map(signed=True, max_exponent_bits=7, total_bits=8):
@@ -239,17 +253,18 @@ class AdamW8bit:
     both moments as uint8 codes of the dynamic maps (exp_avg signed, exp_avg_sq unsigned) in blocks of block_size elements with one fp32 absmax per
     block and moment; the state arenas are byte arenas at the parameter arena's offsets.  Smaller tensors keep fp32 moments.  The update itself is
     tg_adamw_step's fp32 arithmetic on the dequantised moments (where this restates bitsandbytes).  Build the arena with moments=False:
-    the fp32 moment arenas are what this optimizer saves."""
+    the fp32 moment arenas are what this optimizer saves.  stochastic_round / sr_seed: as AdamW's (tg_adamw8bit_step_sr)."""
 
     KIND = "adamw8bit"
 
     def __init__(self, arena, lr=2e-4, betas=(0.9, 0.95), eps=1e-8, weight_decay=1e-4, max_grad_norm=1.0, clip_elems=None, min_8bit_size=4096,
-                 block_size=2048):
+                 block_size=2048, stochastic_round=False, sr_seed=0):
         if block_size not in (256, 512, 1024, 2048):
             raise ValueError(f"AdamW8bit: block_size {block_size} not in (256, 512, 1024, 2048)")
         self.arena, self.lr, self.betas, self.eps, self.wd, self.max_norm = arena, lr, tuple(betas), eps, weight_decay, max_grad_norm
         self.clip_elems = arena.numel if clip_elems is None else int(clip_elems)
         self.min_8bit_size, self.block_size = int(min_8bit_size), int(block_size)
+        self.stochastic_round, self.sr_seed = bool(stochastic_round), _sr_seed(sr_seed)
         self.t = 0
         dev = arena.param.device
         self.rows, n_absmax, n_small = block_table(arena, self.block_size, self.min_8bit_size, self.clip_elems)
@@ -279,20 +294,25 @@ class AdamW8bit:
         if self.max_norm is not None and self.max_norm > 0 and nc > 0:
             L.check(lib.tg_grad_clip_coef(a.grad.data_ptr(), nc, float(self.max_norm), self._ws.data_ptr(), self.coef.data_ptr(), st), "tg_grad_clip_coef")
             clip_ptr = self.coef.data_ptr() + 4
-        L.check(lib.tg_adamw8bit_step(a.param.data_ptr(), a.grad.data_ptr(), self.state1.data_ptr(), self.state2.data_ptr(), self.absmax1.data_ptr(),
-                                      self.absmax2.data_ptr(), self.small_m.data_ptr(), self.small_v.data_ptr(), self.qmap1.data_ptr(), self.qmap2.data_ptr(),
-                                      self._table.data_ptr(), len(self.rows), self.nblocks, self.block_size, self.t, float(lr), float(self.betas[0]),
-                                      float(self.betas[1]), float(self.eps), float(self.wd), clip_ptr, 1 if zero_grad else 0, st), "tg_adamw8bit_step")
+        args = (a.param.data_ptr(), a.grad.data_ptr(), self.state1.data_ptr(), self.state2.data_ptr(), self.absmax1.data_ptr(), self.absmax2.data_ptr(),
+                self.small_m.data_ptr(), self.small_v.data_ptr(), self.qmap1.data_ptr(), self.qmap2.data_ptr(), self._table.data_ptr(), len(self.rows),
+                self.nblocks, self.block_size, self.t, float(lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.wd), clip_ptr,
+                1 if zero_grad else 0)
+        if self.stochastic_round:
+            L.check(lib.tg_adamw8bit_step_sr(*args, self.sr_seed, st), "tg_adamw8bit_step_sr")
+        else:
+            L.check(lib.tg_adamw8bit_step(*args, st), "tg_adamw8bit_step")
 
     # ---- checkpoint / resume, as AdamW: {"t", "state1" / "state2": the uint8 code arenas, "absmax1" / "absmax2", "small_m" / "small_v": the fp32
-    # moments of the small tensors, "grad", "layout", "hyper": AdamW's keys + kind / block_size / min_8bit_size}
+    # moments of the small tensors, "grad", "layout", "hyper": AdamW's keys (stochastic_round / sr_seed among them) + kind / block_size / min_8bit_size}
     _STATE = ("state1", "state2", "absmax1", "absmax2", "small_m", "small_v")
 
     def state_dict(self):
         a = self.arena
         sd = {"t": int(self.t), "grad": a.grad.detach().cpu().clone(), "layout": a.layout(),
               "hyper": {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd, "max_grad_norm": self.max_norm,
-                        "clip_elems": self.clip_elems, "kind": self.KIND, "block_size": self.block_size, "min_8bit_size": self.min_8bit_size}}
+                        "clip_elems": self.clip_elems, "kind": self.KIND, "block_size": self.block_size, "min_8bit_size": self.min_8bit_size,
+                        "stochastic_round": self.stochastic_round, "sr_seed": self.sr_seed}}
         for name in self._STATE:
             sd[name] = getattr(self, name).detach().cpu().clone()
         return sd
@@ -318,6 +338,7 @@ class AdamW8bit:
         self.t = int(sd["t"])
         self.lr, self.betas, self.eps = h.get("lr", self.lr), tuple(h.get("betas", self.betas)), h.get("eps", self.eps)
         self.wd, self.max_norm = h.get("weight_decay", self.wd), h.get("max_grad_norm", self.max_norm)
+        self.stochastic_round, self.sr_seed = bool(h.get("stochastic_round", False)), _sr_seed(h.get("sr_seed", 0))
         if int(h.get("clip_elems", self.clip_elems)) != self.clip_elems:
             raise ValueError(f"AdamW8bit.load_state_dict: the checkpoint's clip_elems is {h.get('clip_elems')}, this optimizer's is {self.clip_elems} "
                              "(the table's clipped flags are fixed at construction)")
@@ -437,7 +458,10 @@ def get_optimizer(arena, cfg, clip_elems=None):
     prodigy_safeguard_warmup (argparse defaults where a key is missing).  `cfg`: a dict or an object with those attributes.  "adamw" -> AdamW,
     "adamw" + use_8bit_adam -> AdamW8bit (build the arena with moments=False), "prodigy" -> Prodigy (arena with moments=True; warns when
     learning_rate <= 0.1, as the reference does); use_8bit_adam with another optimizer is ignored with a warning, an unknown optimizer falls back to
-    "adamw" with a warning; "adam" raises NotImplementedError."""
+    "adamw" with a warning; "adam" raises NotImplementedError.  One key of this project's own: bf16_stochastic_round (default False) turns on the
+    stochastic bf16 parameter write of AdamW / AdamW8bit, seeded by the yaml's `seed` (default 0) — the SAME seed on every rank, the rank is not
+    mixed in, so data-parallel ranks keep bitwise-equal parameters; with "prodigy" it is ignored with a warning (Prodigy writes bf16(p0 + delta)
+    from an exact fp32 delta: nothing is lost to the rounding there)."""
     get = cfg.get if isinstance(cfg, dict) else (lambda k, d=None: getattr(cfg, k, d))
     name = str(get("optimizer", "adam")).lower()
     if name not in ("adam", "adamw", "prodigy"):
@@ -450,7 +474,11 @@ def get_optimizer(arena, cfg, clip_elems=None):
     if name == "adam":
         raise NotImplementedError("optimizer 'adam' (torch.optim.Adam / bitsandbytes Adam8bit: weight decay added to the gradient) is not implemented; "
                                   "the training yamls use 'adamw'")
+    sr = bool(get("bf16_stochastic_round", False))
     if name == "prodigy":
+        if sr:
+            warnings.warn("bf16_stochastic_round is ignored when optimizer is 'prodigy': Prodigy keeps the update in an exact fp32 delta and writes "
+                          "bf16(p0 + delta), so no update is lost to the rounding")
         lr = float(get("learning_rate", 1e-4))
         if lr <= 0.1:
             warnings.warn("Learning rate is too low. When using prodigy, it's generally better to set learning rate around 1.0")
@@ -461,7 +489,7 @@ def get_optimizer(arena, cfg, clip_elems=None):
                        safeguard_warmup=bool(get("prodigy_safeguard_warmup", False)), max_grad_norm=float(get("max_grad_norm", 1.0)), clip_elems=clip_elems)
     kw = dict(lr=float(get("learning_rate", 1e-4)), betas=(float(get("adam_beta1", 0.9)), float(get("adam_beta2", 0.95))),
               eps=float(get("adam_epsilon", 1e-8)), weight_decay=float(get("adam_weight_decay", 1e-4)), max_grad_norm=float(get("max_grad_norm", 1.0)),
-              clip_elems=clip_elems)
+              clip_elems=clip_elems, stochastic_round=sr, sr_seed=get("seed", 0))
     return AdamW8bit(arena, **kw) if use_8bit else AdamW(arena, **kw)
 
 
