@@ -625,7 +625,8 @@ int tg_pca_lowrank_filter(const void* x, long ldx, const float* comp, const floa
  * voxel (3 used; HARD PRECONDITION: channels 3..7 of x and cache are finite — the kernel's padded reduction entries multiply them by zero weights, so a NaN / Inf
  * there would reach all 128 outputs; tokensgen_amd.vae zero-fills them), w is packed [128][96] with reduction index k = tap * 3 + channel (81 real entries, the rest zero), cout = cout_pad = 128.
  * The decoder's conv_out (Cin = 128 -> cout <= 4, 3x3x3) takes a halo-tiled kernel with LDS-resident weights at launch scale; same arguments as any narrow layer.
- * gn_partial (optional, tg_conv3d_gn_partial_floats(To,Ho,Wo) floats; needs cout % 128 == 0): per 128-voxel tile row the sums and
+ * gn_partial (optional, tg_conv3d_gn_partial_floats(To,Ho,Wo) floats; needs cout % 128 == 0 and whole groups per 128-channel tile, 128 % (cout / 32) == 0:
+ * cout in {128, 256, 512, 1024, ...}, not 384): per 128-voxel tile row the sums and
  * sums of squares, per GroupNorm(32) group, of the bf16 values this launch stores — summed in a fixed order — so that the
  * GroupNorm / SpatialNorm that reads y next needs no statistics pass of its own: tg_groupnorm_finalize turns them into
  * (mean, rstd) exactly like the second stage of tg_groupnorm_stats.
@@ -638,6 +639,18 @@ int tg_conv3d_cl(const void* x, int T, int H, int W, int Cin, const void* cache,
                  float* splitk_ws, hipStream_t stream);
 long tg_conv3d_splitk_floats(int Cin, int cout, int cout_pad, int kt, int kh, int kw, int To, int Ho, int Wo);
 long tg_conv3d_gn_partial_floats(int To, int Ho, int Wo);
+
+/* Which kernel tg_conv3d_cl launches for this shape NOW (the TG_CONV_HALO / TG_CONV_W4 / TG_CONV_SPLITK knobs and the device's CU count included; 256 CUs where there
+ * is no device): 0 the 8-channel input convolution, 1 the halo-tiled narrow output (conv_out), 2 the 128 x 16 tile, 3 the halo-tiled 16 x 32 patch, 4 the 4-wave
+ * 256 x 256 tile, 5 the 4-wave 512 x 128 tile, 6 the 128 x 128 tile, 7 the 128 x 128 tile over K ranges + the reduce launch (enum ConvKernel, csrc/conv_plan.h); the
+ * negative error code for a shape tg_conv3d_cl refuses.  has_t_map / has_residual / has_gn_partial: whether the call would pass that optional argument (0 / 1).
+ * A pure host query (no launch, no device needed); the edge tests ask it before every launch, so that a case written for one kernel cannot silently run another.
+ * tg_conv3d_splitk_plan, same arguments: 0 unless the answer above is 7, else ksplit * 16 + the reduce kernel's template case (ksplit if that is 2, 4 or 8, else 0: the
+ * generic loop). */
+long tg_conv3d_kernel(int T, int H, int W, int Cin, int cout, int cout_pad, int kt, int kh, int kw, int stride, int pad, int up, int To, int Ho, int Wo,
+                      int has_t_map, int has_residual, int has_gn_partial);
+long tg_conv3d_splitk_plan(int T, int H, int W, int Cin, int cout, int cout_pad, int kt, int kh, int kw, int stride, int pad, int up, int To, int Ho, int Wo,
+                           int has_t_map, int has_residual, int has_gn_partial);
 
 /* CogVideoXUpsample3D's spatial part — F.interpolate(scale 2, nearest) followed by Conv2d 3x3, padding 1 (diffusers CogVideoXUpsample3D; call site
  * autoencoder_kl_cogvideox.py:849-883, the decoder's up blocks) — as FOUR 2x2 convolutions on the LOW-resolution input, one per output phase (py, px):

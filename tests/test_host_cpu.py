@@ -405,6 +405,45 @@ def test_conv_plan_table():
         assert g == w
 
 
+def test_conv_kernel_query_follows_the_plan_and_the_knobs():
+    """tg_conv3d_kernel / tg_conv3d_splitk_plan (lib.conv3d_kernel, lib.conv3d_splitk_plan): the live plan — conv_plan.h with the TG_CONV_* knobs as they are NOW and
+    tg_device_cus(), which answers 256 without a device — agrees with lines of CONV_PLAN_TABLE above, and follows lib.debug_set and back."""
+    from tokensgen_amd import lib as L
+    q = lambda ci, co, cp, T, H, W, **kw: L.conv3d_kernel(T, H, W, ci, co, cp, 3, 3, 3, **kw)
+    assert q(8, 128, 128, 8, 240, 360) == L.CONV_IN8 == 0
+    assert q(128, 3, 16, 8, 240, 360) == L.CONV_HALO_NARROW == 1 and q(128, 3, 16, 2, 32, 32) == L.CONV_N16 == 2
+    assert q(128, 128, 128, 8, 240, 360) == L.CONV_HALO2 == 3 and q(256, 256, 256, 8, 120, 180) == L.CONV_W4_256 == 4
+    assert q(128, 128, 128, 1, 128, 256) == L.CONV_128 == 6 and q(512, 512, 512, 2, 30, 45) == L.CONV_128_SPLITK == 7
+    plan = lambda ci, co, T, H, W: L.conv3d_splitk_plan(T, H, W, ci, co, co, 3, 3, 3)
+    assert plan(512, 512, 2, 30, 45) == (5, 0) and plan(128, 128, 2, 32, 32) == (6, 0) and plan(256, 256, 1, 32, 32) == (8, 8) and plan(128, 128, 1, 120, 272) == (2, 2)
+    assert L.conv3d_splitk_plan(1, 62, 128, 256, 256, 256, 1, 3, 3) == (4, 4) and plan(128, 128, 1, 128, 256) == (1, 0)
+    # refused shapes: the plan's error code, whichever optional argument makes the shape illegal
+    assert q(100, 128, 128, 2, 8, 8) == -2 and q(8, 64, 64, 2, 8, 8) == -2 and q(128, 3, 16, 2, 8, 8, gn_partial=True) == -2
+    assert q(8, 128, 128, 2, 1, 1) == L.CONV_IN8 and q(8, 128, 128, 2, 1, 1, gn_partial=True) == -2 and q(8, 128, 128, 2, 8, 8, residual=True) == -2
+    assert L.conv3d_kernel(2, 5, 6, 64, 128, 128, 1, 3, 3, up=2, out_dims=(4, 10, 12), t_map=True) == L.CONV_128
+    # fused GroupNorm sums need whole groups per 128-channel tile: 384 channels (12 per group, 10.67 groups per tile) run, but not with the sums; 1024 (32 per group) do
+    assert q(128, 384, 384, 2, 32, 32) == L.CONV_128_SPLITK and q(128, 384, 384, 2, 32, 32, gn_partial=True) == -2 and q(128, 640, 640, 2, 32, 32, gn_partial=True) == -2
+    assert q(128, 1024, 1024, 2, 8, 8, gn_partial=True) == L.CONV_128 and q(128, 512, 512, 2, 8, 8, gn_partial=True) == L.CONV_128_SPLITK
+    # the knobs, live: the shapes of the table's `halo=2`, `halo=0` and `w4=2` lines
+    assert q(128, 128, 128, 2, 32, 32) == L.CONV_128_SPLITK and q(128, 3, 16, 2, 32, 32) == L.CONV_N16
+    old = L.debug_set("TG_CONV_HALO", 2)
+    try:
+        assert old == 1 and q(128, 128, 128, 2, 32, 32) == L.CONV_HALO2 and q(256, 256, 256, 2, 32, 32) == L.CONV_HALO2 and q(128, 3, 16, 2, 32, 32) == L.CONV_HALO_NARROW
+        assert plan(128, 128, 2, 32, 32) == (1, 0)
+        L.debug_set("TG_CONV_HALO", 0)
+        assert q(128, 128, 128, 8, 240, 360) == L.CONV_W4_128 == 5
+    finally:
+        L.debug_set("TG_CONV_HALO", old)
+    assert q(128, 128, 128, 2, 32, 32) == L.CONV_128_SPLITK and q(128, 128, 128, 8, 240, 360) == L.CONV_HALO2
+    assert q(256, 256, 256, 1, 32, 32) == L.CONV_128_SPLITK and q(128, 128, 128, 1, 32, 64) == L.CONV_128_SPLITK
+    old = L.debug_set("TG_CONV_W4", 2)
+    try:
+        assert old == 1 and q(256, 256, 256, 1, 32, 32) == L.CONV_W4_256 and q(128, 128, 128, 1, 32, 64) == L.CONV_W4_128 and q(128, 128, 128, 1, 23, 89) == L.CONV_128_SPLITK
+    finally:
+        L.debug_set("TG_CONV_W4", old)
+    assert q(256, 256, 256, 1, 32, 32) == L.CONV_128_SPLITK
+
+
 GEMM_PLAN_TABLE = """
     plain 28326x3072->9216: k256w4 grid 256 block 256 lds 150784 group_m 4
     plain 28326x12288->3072: k256w4 grid 256 block 256 lds 150784 group_m 1

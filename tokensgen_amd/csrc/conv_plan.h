@@ -39,7 +39,7 @@ struct ConvShape {
 // (A/B runs, and the bitwise 4-wave-vs-128 test)
 struct ConvKnobs { int halo, w4, splitk; };
 
-enum ConvKernel {
+enum ConvKernel {      // the values are tg_conv3d_kernel()'s answers (include/tokensgen_hip.h)
     CONV_IN8,           // conv3d_in_kernel: the encoder's conv_in, 8-channel input
     CONV_HALO_NARROW,   // conv3d_halo_narrow_kernel<128, 3>: the decoder's conv_out
     CONV_N16,           // conv3d_cl_kernel<1, 2, 1>: 128 voxels x 16 channels
@@ -116,7 +116,9 @@ inline ConvPlan conv_plan(const ConvShape& s, const ConvKnobs& knobs, int n_cu) 
                       "tg_conv3d_cl: need Cin%%64==0 and cout_pad%%128==0 (or cout_pad in {16, 32, ..., 112}) (Cin=%d cout=%d cout_pad=%d)", Cin, cout, cout_pad);
     CONV_PLAN_REQUIRE(kt >= 1 && kt <= 3 && kh >= 1 && kh <= 3 && kw >= 1 && kw <= 3 && (stride == 1 || stride == 2) && (up == 1 || up == 2) && pad >= 0 && pad <= 1,
                       "tg_conv3d_cl: unsupported kernel/stride/pad/up");
-    CONV_PLAN_REQUIRE(!s.gn_partial || (cout == cout_pad && cout % BN == 0 && (cout / GN_GROUPS) % 4 == 0),
+    // BN % (cout / 32): every epilogue gives a 128-channel tile BN / (cout / 32) whole groups.  cout = 384 (12 channels per group: 10.67 groups per tile) passed the
+    // first two conditions alone and got sums that missed the channels of every group straddling a tile
+    CONV_PLAN_REQUIRE(!s.gn_partial || (cout == cout_pad && cout % BN == 0 && (cout / GN_GROUPS) % 4 == 0 && BN % (cout / GN_GROUPS) == 0),
                       "tg_conv3d_cl: fused GroupNorm sums need cout in {128, 256, 512, ...} (cout=%d)", cout);
     const long nk = (long)kt * kh * kw * (Cin / BK);    // K steps of 64
     const bool halo_scale = knobs.halo == 2 || h2tiles >= n_cu;
@@ -152,7 +154,8 @@ inline ConvPlan conv_plan(const ConvShape& s, const ConvKnobs& knobs, int n_cu) 
     const long tiles256 = ((M + 255) / 256) * (cout / 256), tiles512 = (M + 511) / 512;
     if (w4_ok && (knobs.w4 == 2 || tiles256 >= n_cu / 8) && cout == cout_pad && cout % 256 == 0 && M >= 1024)
         return launch(CONV_W4_256, tiles256, 256, CW_LDS);
-    // Cout = 128: the 512x128 variant (plain 3x3x3 / 1x3x3 convolutions only: 16 A pieces per wave are too many for the general address path)
+    // Cout = 128: the 512x128 variant ("plain" convolutions only — stride 1, no upsampling, whatever the taps: 3x3x3, 1x3x3, and the 1x1x1, pad 0 shortcut of the
+    // decoder's last 256 -> 128 block, nk = 4, which takes this branch at full size; 16 A pieces per wave are too many for the general address path)
     // (TG_CONV_W4 governs this variant too; measured: 128->128 layers 203 -> 187 ms per decode, 181 -> 162 ms per encode)
     if (w4_ok && (knobs.w4 == 2 || tiles512 >= 2L * n_cu) && cout == 128 && cout_pad == 128 && stride == 1 && up == 1 && M >= 2048)
         return launch(CONV_W4_128, tiles512, 256, CW_LDS_N128);

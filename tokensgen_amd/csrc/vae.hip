@@ -1669,14 +1669,18 @@ inline unsigned grid_for(long total, int block = 256) { return (unsigned)min((to
 }  // namespace
 
 // Which kernel, grid and LDS size: conv_plan() (conv_plan.h), a pure function of the shape, the three TG_CONV_* knobs and the CU count.  Here: what depends
-// on addresses, and the launch.
+// on addresses, and the launch.  live_conv_plan: the plan with the live knobs and the current device's CUs, for the launcher and for the two queries below it
+// (tg_device_cus() answers 256 CUs where there is no device, so the queries also work on a host without a GPU).
+static ConvPlan live_conv_plan(const ConvShape& s) {
+    return conv_plan(s, ConvKnobs{(int)tg_knob(TG_KNOB_CONV_HALO), (int)tg_knob(TG_KNOB_CONV_W4), tg_knob(TG_KNOB_CONV_SPLITK) != 0}, tg_device_cus());
+}
+
 extern "C" int tg_conv3d_cl(const void* x, int T, int H, int W, int Cin, const void* cache, const void* w, const void* bias,
                             int cout, int cout_pad, int kt, int kh, int kw, int stride, int pad, int up, const int32_t* t_map,
                             const void* residual, void* y, long ldy, int To, int Ho, int Wo, const void* zeros, float* gn_partial,
                             float* splitk_ws, hipStream_t stream) {
     TG_REQUIRE(x && w && y && zeros, TG_ERR_ARG, "tg_conv3d_cl: null pointer");
-    const ConvPlan pl = conv_plan(ConvShape{T, H, W, Cin, cout, cout_pad, kt, kh, kw, stride, pad, up, To, Ho, Wo, t_map != nullptr, residual != nullptr, gn_partial != nullptr},
-                                  ConvKnobs{(int)tg_knob(TG_KNOB_CONV_HALO), (int)tg_knob(TG_KNOB_CONV_W4), tg_knob(TG_KNOB_CONV_SPLITK) != 0}, tg_device_cus());
+    const ConvPlan pl = live_conv_plan(ConvShape{T, H, W, Cin, cout, cout_pad, kt, kh, kw, stride, pad, up, To, Ho, Wo, t_map != nullptr, residual != nullptr, gn_partial != nullptr});
     TG_REQUIRE(pl.err == TG_OK, pl.err, "%s", pl.msg);      // every shape error comes before the alignment error (a call with both faults gets the shape one)
     const bool y_x4 = (((uintptr_t)y) & 7) == 0 && ldy % 4 == 0;      // 8-byte stores of four output channels
     TG_REQUIRE(tg_aligned16(x) && tg_aligned16(w) && (!cache || tg_aligned16(cache)) &&
@@ -1721,6 +1725,19 @@ extern "C" int tg_conv3d_cl(const void* x, int T, int H, int W, int Cin, const v
     return TG_OK;
 }
 
+extern "C" long tg_conv3d_kernel(int T, int H, int W, int Cin, int cout, int cout_pad, int kt, int kh, int kw, int stride, int pad, int up, int To, int Ho, int Wo,
+                                 int has_t_map, int has_residual, int has_gn_partial) {
+    const ConvPlan pl = live_conv_plan(ConvShape{T, H, W, Cin, cout, cout_pad, kt, kh, kw, stride, pad, up, To, Ho, Wo, has_t_map != 0, has_residual != 0, has_gn_partial != 0});
+    return pl.err == TG_OK ? (long)pl.kernel : (long)pl.err;
+}
+
+extern "C" long tg_conv3d_splitk_plan(int T, int H, int W, int Cin, int cout, int cout_pad, int kt, int kh, int kw, int stride, int pad, int up, int To, int Ho, int Wo,
+                                      int has_t_map, int has_residual, int has_gn_partial) {
+    const ConvPlan pl = live_conv_plan(ConvShape{T, H, W, Cin, cout, cout_pad, kt, kh, kw, stride, pad, up, To, Ho, Wo, has_t_map != 0, has_residual != 0, has_gn_partial != 0});
+    if (pl.err != TG_OK) return pl.err;
+    return pl.kernel == CONV_128_SPLITK ? 16L * pl.ksplit + pl.reduce_ks : 0;
+}
+
 // tg_device_cus(), as in the launcher: it answers 256 CUs where there is no device, so the query also works on a host without a GPU
 extern "C" long tg_conv3d_splitk_floats(int Cin, int cout, int cout_pad, int kt, int kh, int kw, int To, int Ho, int Wo) {
     return conv_splitk_floats(Cin, cout, cout_pad, kt, kh, kw, To, Ho, Wo, tg_knob(TG_KNOB_CONV_SPLITK) != 0, tg_device_cus());
@@ -1758,7 +1775,8 @@ extern "C" int tg_conv3d_up2_subpixel(const void* x, int T, int H, int W, int Ci
                "tg_conv3d_up2_subpixel: shape outside the 256 x 256 kernel's range (T=%d H=%d W=%d Cin=%d cout=%d): ask tg_conv3d_up2_subpixel_ok first", T, H, W, Cin, cout);
     TG_REQUIRE(tg_aligned16(x) && tg_aligned16(w_phases) && tg_aligned16(zeros) && (((uintptr_t)y) & 7) == 0 && ldy % 4 == 0 && ldy >= cout, TG_ERR_ALIGN,
                "tg_conv3d_up2_subpixel: alignment");
-    TG_REQUIRE(!gn_partial || (cout / GN_GROUPS) % 4 == 0, TG_ERR_SHAPE, "tg_conv3d_up2_subpixel: fused GroupNorm sums need cout in {256, 512, ...}");
+    TG_REQUIRE(!gn_partial || ((cout / GN_GROUPS) % 4 == 0 && 256 % (cout / GN_GROUPS) == 0), TG_ERR_SHAPE,
+               "tg_conv3d_up2_subpixel: fused GroupNorm sums need cout in {256, 512, 1024, ...} (whole groups per 256-channel tile)");
     const long M = (long)T * H * W, tiles = ((M + 255) / 256) * (cout / 256);
     TG_DYN_LDS((conv3d_w4_kernel<256>), CW_LDS);
     // ONE launch for the four phases (virtual tile = phase * tiles + tile; the kernel derives the phase's padding — rows yl + a - (1 - py): phase 0 reads (yl - 1, yl),

@@ -717,7 +717,7 @@ def conv3d_cl(x, w_packed, bias, cout, kt, kh, kw, cache=None, stride=1, pad=1, 
         _chk(residual, "residual"); assert residual.is_contiguous() and residual.shape == y.shape
     if t_map is not None:
         _chk(t_map, "t_map", torch.int32)
-    fuse = gn_stats_eps is not None and cout % 128 == 0 and w_packed.shape[0] == cout
+    fuse = gn_stats_eps is not None and cout % 128 == 0 and w_packed.shape[0] == cout and 128 % (cout // 32) == 0      # whole groups per 128-channel tile (conv_plan.h)
     partial = torch.empty(L.load().tg_conv3d_gn_partial_floats(To, Ho, Wo), dtype=torch.float32, device=x.device) if fuse else None
     nws = _splitk_floats(Cin, cout, w_packed.shape[0], kt, kh, kw, To, Ho, Wo)
     ws = torch.empty(nws, dtype=torch.float32, device=x.device) if nws else None
@@ -744,7 +744,7 @@ def conv3d_up2_subpixel(x, w_phases, bias, cout, gn_stats_eps=None, time_x2=Fals
     assert tuple(w_phases.shape) == (4, cout, 4, Cin)
     To = T if not (time_x2 and T > 1) else (2 * T - 1 if T % 2 else 2 * T)        # time_x2: every frame twice, except the first of an odd count (CogVideoXUpsample3D)
     y = torch.empty(To, 2 * H, 2 * W, cout, dtype=BF16, device=x.device)
-    fuse = gn_stats_eps is not None
+    fuse = gn_stats_eps is not None and cout % 256 == 0 and 256 % (cout // 32) == 0     # whole groups per 256-channel tile
     partial = torch.empty(L.load().tg_conv3d_up2_subpixel_gn_floats(T, H, W), dtype=torch.float32, device=x.device) if fuse else None
     L.check(_launch(f"conv3d_up2_subpixel_Cin{Cin}_Cout{cout}_t{int(bool(time_x2))}", L.load().tg_conv3d_up2_subpixel, _p(x), T, H, W, Cin, _p(w_phases), _p(bias), cout, _p(y), cout,
                     1 if time_x2 else 0, _p(zero_page(x.device)), _p(partial), _stream()), "tg_conv3d_up2_subpixel")

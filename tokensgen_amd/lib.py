@@ -111,6 +111,8 @@ QUERIES = {
     "tg_conv3d_up2_subpixel_ok": [C.c_int] * 5,
     "tg_groupnorm_reduce_rows": [C.c_long],
     "tg_conv3d_splitk_floats": [C.c_int] * 9,
+    "tg_conv3d_kernel": [C.c_int] * 18,
+    "tg_conv3d_splitk_plan": [C.c_int] * 18,
     "tg_attention_bwd_ws_floats": [C.c_int, C.c_int, C.c_int, C.c_int],
     "tg_attention_bwd_probe_bytes": [],
     "tg_attention_retry_ints": [C.c_int, C.c_int, C.c_int, C.c_int],
@@ -185,6 +187,29 @@ def gemm_kernel(M, N, K, lda=0, ldw=0):
     """tg_gemm_kernel: what the library launches for this shape NOW (csrc/gemm_plan.h, the TG_GEMM_W4 knob included): 0 the 128x128 tile, 1 the 8-wave 256x256
     kernel, 2 the 4-wave one, < 0 a refused shape.  A leading dimension left at 0 means contiguous rows (K)."""
     return load().tg_gemm_kernel(M, N, K, lda or K, ldw or K)
+
+
+# tg_conv3d_kernel's answers (enum ConvKernel, csrc/conv_plan.h)
+CONV_IN8, CONV_HALO_NARROW, CONV_N16, CONV_HALO2, CONV_W4_256, CONV_W4_128, CONV_128, CONV_128_SPLITK = range(8)
+
+
+def _conv_query_args(T, H, W, Cin, cout, cout_pad, kt, kh, kw, stride, pad, up, out_dims, t_map, residual, gn_partial):
+    To, Ho, Wo = out_dims if out_dims is not None else (T, H, W)
+    return (T, H, W, Cin, cout, cout_pad, kt, kh, kw, stride, pad, up, To, Ho, Wo, int(bool(t_map)), int(bool(residual)), int(bool(gn_partial)))
+
+
+def conv3d_kernel(T, H, W, Cin, cout, cout_pad, kt, kh, kw, stride=1, pad=1, up=1, out_dims=None, t_map=False, residual=False, gn_partial=False):
+    """tg_conv3d_kernel: which kernel tg_conv3d_cl launches for this shape NOW (csrc/conv_plan.h with the live TG_CONV_* knobs): one of the CONV_* values above, < 0 a
+    refused shape.  out_dims left at None means (T, H, W); t_map / residual / gn_partial: whether the call would pass that optional argument."""
+    return load().tg_conv3d_kernel(*_conv_query_args(T, H, W, Cin, cout, cout_pad, kt, kh, kw, stride, pad, up, out_dims, t_map, residual, gn_partial))
+
+
+def conv3d_splitk_plan(T, H, W, Cin, cout, cout_pad, kt, kh, kw, stride=1, pad=1, up=1, out_dims=None, t_map=False, residual=False, gn_partial=False):
+    """tg_conv3d_splitk_plan: (ksplit, template case of the reduce kernel: 2, 4, 8, or 0 for its generic loop) of a CONV_128_SPLITK launch, (1, 0) for every other kernel."""
+    v = load().tg_conv3d_splitk_plan(*_conv_query_args(T, H, W, Cin, cout, cout_pad, kt, kh, kw, stride, pad, up, out_dims, t_map, residual, gn_partial))
+    if v < 0:
+        raise RuntimeError(f"tg_conv3d_splitk_plan: tg_conv3d_cl refuses this shape ({v})")
+    return (v >> 4, v & 15) if v else (1, 0)
 
 
 def check(code, what):

@@ -60,6 +60,16 @@ def pack_up2_phases(w):
     return out.to(BF16).contiguous()
 
 
+def pack_conv_in_k96(w):
+    """The encoder's input convolution [128, 3, 3, 3, 3] -> [128][96] bf16 with reduction index k = tap * 3 + channel (81 real entries, the rest zero): the weights of
+    tg_conv3d_cl's Cin = 8 form (csrc/vae.hip conv3d_in_kernel), whose input tiles carry 8 channels."""
+    co, ci = w.shape[:2]
+    assert (co, ci) == (128, 3) and tuple(w.shape[2:]) == (3, 3, 3)
+    out = torch.zeros(co, 96, dtype=BF16, device=w.device)
+    out[:, :81] = w.reshape(co, ci, 27).permute(0, 2, 1).reshape(co, 81)
+    return out.contiguous()
+
+
 class AutoencoderKLCogVideoX:
     def __init__(self, in_channels=3, out_channels=3, block_out_channels=(128, 256, 256, 512), latent_channels=16, layers_per_block=3,
                  act_fn="silu", norm_eps=1e-6, norm_num_groups=32, temporal_compression_ratio=4, sample_height=480, sample_width=720,
@@ -139,9 +149,7 @@ class AutoencoderKLCogVideoX:
                     continue                                                               # SpatialNorm convs: fused below
                 if k == "encoder.conv_in.conv.weight" and ci == 3 and co == 128 and tuple(taps) == (3, 3, 3):
                     # the encoder's input convolution: reduction index k = tap * 3 + channel (81 -> 96), input tiles carry 8 channels (csrc/vae.hip conv3d_in_kernel)
-                    w = torch.zeros(co, 96, dtype=BF16, device=self.device)
-                    w[:, :81] = v.reshape(co, ci, 27).permute(0, 2, 1).reshape(co, 81)
-                    self._packed[k + ".k96"] = w.contiguous()          # beside the general packing: tiles too small for the patch kernel take that
+                    self._packed[k + ".k96"] = pack_conv_in_k96(v)     # beside the general packing: tiles too small for the patch kernel take that
                 if ".upsamplers." in k and tuple(taps) == (3, 3) and co % 256 == 0 and ci % 64 == 0:
                     self._packed[k + ".up2"] = pack_up2_phases(v)       # beside the general packing (time-upsampling layers and small tiles keep that)
                 cin_p = _pad_to(ci, 64)
