@@ -805,6 +805,35 @@ int tg_t5_attention(const void* q, const void* k, const void* v, long ld, long s
 int tg_gated_gelu(const void* h, long ldh, void* out, long ldo, long rows, int F, hipStream_t stream);
 int tg_residual_add(const void* x, const void* y, void* out, long n, hipStream_t stream);
 
+/* The ViT image encoders and the frame-consistency metric on their features (csrc/vit.hip; host side: tokensgen_amd/vit.py and metrics.py):
+ * transformers' ViTModel (no pooler) and CLIPVisionModelWithProjection, pre-LayerNorm ViTs with heads of 64.  Every projection, the patch convolution included, is
+ * tg_gemm_bf16 with TG_EPI_BIAS; the attention is tg_t5_attention with q_proj pre-scaled by 1/8 at load and a zero bias table; the residual is tg_residual_add.
+ * These five exports are the rest.
+ * tg_vit_patch_rows: out[(f * H/p + py) * W/p + px][(c * p + dy) * p + dx] = bf16( fp32(x[f][c][py * p + dy][px * p + dx]) * a[c] + b[c] ) (one fused multiply-add),
+ *   columns 3 p^2 .. Kp - 1 written as zeros — the rows of the patch convolution as a GEMM against conv.weight.reshape(D, -1), with the image preprocessing
+ *   ((x + 1) / 2 - mean_c) / std_c folded into a[c] = 0.5 / std_c, b[c] = (0.5 - mean_c) / std_c.  x: bf16 [F][3][H][W], H % p == 0, W % p == 0, p <= 256; a, b: HOST
+ *   pointers to 3 floats each (passed to the kernel by value); Kp must be 3 p^2 rounded up to a multiple of 64 (TG_ERR_SHAPE otherwise).  x, out 16-byte aligned.
+ * tg_vit_assemble: tok[f][0][:] = bf16( fp32(cls[:]) + fp32(pos[0][:]) ), tok[f][1 + i][:] = bf16( fp32(patch[f * P + i][:]) + fp32(pos[1 + i][:]) ) — the
+ *   embeddings of both models.  patch bf16 [F * P][D] contiguous, cls bf16 [D], pos bf16 [P + 1][D], tok bf16 [F][P + 1][D]; D % 64 == 0; all 16-byte aligned.
+ * tg_layernorm: y[r][c] = bf16( (x[r][c] - mean_r) * rsqrt(var_r + eps) * w[c] + b[c] ) — nn.LayerNorm: mean_r = sum_c x / D, then var_r = sum_c (x - mean_r)^2 / D
+ *   from the row held in registers, both sums in fp32 in a fixed order.  One wave per row: a row's result depends on that row alone.  x [rows][D] with row stride
+ *   ldx, y with ldy (the final norm of an encoder runs on the class-token rows only, ldx = S * D); D % 64 == 0 and D <= 4096 (TG_ERR_SHAPE otherwise); x, w, b, y
+ *   16-byte aligned, ldx and ldy multiples of 8.  A constant row gives b wherever its fp32 sum is exact.
+ * tg_vit_act: y[i] = bf16( act(fp32(x[i])) ), mode 0: exact GELU 0.5 x (1 + erf(x / sqrt 2)), evaluated as 0.5 x erfc(-x / sqrt 2) (the same function without the
+ *   cancellation in the negative tail); mode 1: quick GELU x * sigmoid(1.702 x).  n % 8 == 0, any number of workgroups' worth; x, y 16-byte aligned, y may be x.
+ * tg_feature_consistency: prev_out[o] = max(0, cos(f_i, f_{i-1})), first_out[o] = max(0, cos(f_i, f_first)) in float64, with
+ *   cos(x, y) = x . y / (max(|x|, 1e-8) * max(|y|, 1e-8)) — torch.nn.functional.cosine_similarity in float64, a zero row giving 0.  feat: fp32 [F][D] with row stride
+ *   ld.  Without carried rows (first_row == prev_row == NULL): f_first = feat[0], outputs for i = 1 .. F - 1 (o = i - 1, F >= 2).  With both carried rows (fp32 [D],
+ *   the first and the last feature of the video so far): f_first = first_row, f_{-1} = prev_row, outputs for i = 0 .. F - 1 (o = i, F >= 1).  One carried row without
+ *   the other: TG_ERR_ARG.  All sums float64 in a fixed order, no atomics: bitwise reproducible, and an output depends on its three rows alone, so a video fed in
+ *   pieces gives the bits of the video fed whole.  feat 4-byte aligned, outputs 8-byte aligned. */
+int tg_vit_patch_rows(const void* x, int F, int H, int W, int p, const float* a, const float* b, void* out, int Kp, hipStream_t stream);
+int tg_vit_assemble(const void* patch, const void* cls, const void* pos, void* tok, int F, int P, int D, hipStream_t stream);
+int tg_layernorm(const void* x, long ldx, const void* w, const void* b, void* y, long ldy, long rows, int D, float eps, hipStream_t stream);
+int tg_vit_act(const void* x, void* y, long n, int mode, hipStream_t stream);
+int tg_feature_consistency(const float* feat, long ld, int F, int D, const float* first_row, const float* prev_row, double* prev_out, double* first_out,
+                           hipStream_t stream);
+
 /* Dispatch overrides for the cross-check tests — NOT part of the operator surface.  The library reads no environment variable and keeps no other
  * process-wide state: the defaults are the shipped path, and these knobs only choose between two PRODUCT kernels of the same operator (each pair is held
  * bitwise or to rounding against each other by tests/).  Knobs: TG_ATTN_PP_MIN_WG (1024: workgroups from which the 8-wave attention kernel is used),

@@ -1099,3 +1099,73 @@ def residual_add(x, y, out):
         raise ValueError(f"residual_add: expected three contiguous tensors of one shape, got {tuple(x.shape)}, {tuple(y.shape)}, {tuple(out.shape)}")
     L.check(_launch("residual_add", L.load().tg_residual_add, _p(x), _p(y), _p(out), x.numel(), _stream()), "tg_residual_add")
     return out
+
+
+def vit_patch_rows(frames, patch, a, b, out):
+    """tg_vit_patch_rows: frames bf16 [F, 3, H, W] contiguous -> out[:F * (H / patch) * (W / patch)] (out: contiguous [rows >= that, Kp], Kp = 3 patch^2 rounded up
+    to a multiple of 64) = bf16(frames * a[c] + b[c]) in the column order (c, dy, dx), pad columns zero.  a, b: three Python floats each."""
+    _chk(frames, "frames"); _chk(out, "out")
+    if frames.dim() != 4 or frames.shape[1] != 3 or not frames.is_contiguous() or out.dim() != 2 or not out.is_contiguous():
+        raise ValueError(f"vit_patch_rows: expected contiguous frames [F, 3, H, W] and out [rows, Kp], got {tuple(frames.shape)} and {tuple(out.shape)}")
+    F, _, H, W = frames.shape
+    if H % patch or W % patch or out.shape[0] < F * (H // patch) * (W // patch):
+        raise ValueError(f"vit_patch_rows: {H} x {W} frames do not divide into patches of {patch}, or out{tuple(out.shape)} has too few rows")
+    fa, fb = (C.c_float * 3)(*a), (C.c_float * 3)(*b)
+    L.check(_launch("vit_patch_rows", L.load().tg_vit_patch_rows, _p(frames), F, H, W, int(patch), fa, fb, _p(out), out.shape[1], _stream()), "tg_vit_patch_rows")
+    return out
+
+
+def vit_assemble(patch, cls, pos, tok):
+    """tg_vit_assemble: tok [F, S, D] = (cls | patch[f * P + i]) + pos, S = P + 1; patch contiguous [rows >= F * P, D], cls [D], pos [S, D], all bf16."""
+    _chk(patch, "patch"); _chk(cls, "cls"); _chk(pos, "pos"); _chk(tok, "tok")
+    if tok.dim() != 3 or not (tok.is_contiguous() and patch.is_contiguous() and cls.is_contiguous() and pos.is_contiguous()):
+        raise ValueError("vit_assemble: expected contiguous tok [F, S, D], patch [rows, D], cls [D] and pos [S, D]")
+    F, S, D = tok.shape
+    if patch.dim() != 2 or patch.shape[1] != D or patch.shape[0] < F * (S - 1) or cls.numel() != D or tuple(pos.shape) != (S, D) or S < 2:
+        raise ValueError(f"vit_assemble: tok{tuple(tok.shape)} needs patch [>= {F * (S - 1)}, {D}], cls [{D}] and pos [{S}, {D}]; got {tuple(patch.shape)}, "
+                         f"{tuple(cls.shape)}, {tuple(pos.shape)}")
+    L.check(_launch("vit_assemble", L.load().tg_vit_assemble, _p(patch), _p(cls), _p(pos), _p(tok), F, S - 1, D, _stream()), "tg_vit_assemble")
+    return tok
+
+
+def layernorm(x, weight, bias, out, eps):
+    """tg_layernorm (nn.LayerNorm over the last dimension): x, out [rows, D] views with one row stride each (D % 64 == 0, D <= 4096), weight and bias [D]."""
+    _chk(x, "x"); _chk(weight, "weight"); _chk(bias, "bias"); _chk(out, "out")
+    D = x.shape[-1]
+    if x.dim() != 2 or out.shape != x.shape or tuple(weight.shape) != (D,) or tuple(bias.shape) != (D,) or not (weight.is_contiguous() and bias.is_contiguous()):
+        raise ValueError(f"layernorm: expected x and out [rows, D] of one shape, weight and bias [D]; got {tuple(x.shape)}, {tuple(out.shape)}, {tuple(weight.shape)}")
+    L.check(_launch("layernorm", L.load().tg_layernorm, _p(x), x.stride(0), _p(weight), _p(bias), _p(out), out.stride(0), x.shape[0], D, float(eps), _stream()),
+            "tg_layernorm")
+    return out
+
+
+VIT_ACT = {"gelu": 0, "quick_gelu": 1}
+
+
+def vit_act(x, out, mode):
+    """tg_vit_act: out = bf16(act(x)) on two contiguous bf16 tensors of one shape (out may be x); mode "gelu" (the exact, erf form) or "quick_gelu"."""
+    _chk(x, "x"); _chk(out, "out")
+    if x.shape != out.shape or not (x.is_contiguous() and out.is_contiguous()):
+        raise ValueError(f"vit_act: expected two contiguous tensors of one shape, got {tuple(x.shape)} and {tuple(out.shape)}")
+    L.check(_launch("vit_act", L.load().tg_vit_act, _p(x), _p(out), x.numel(), VIT_ACT[mode], _stream()), "tg_vit_act")
+    return out
+
+
+def feature_consistency(feat, first=None, prev=None):
+    """tg_feature_consistency: feat fp32 [F, D] (a row stride allowed) -> (prev, first), float64 [F - 1]: max(0, cos) of frames 1 .. F - 1 with their predecessor and
+    with frame 0.  With the carried rows `first` and `prev` (fp32 [D], both or neither: the first and the last feature of the video so far) -> float64 [F], frame 0
+    compared with `prev`, every frame with `first`."""
+    _chk(feat, "feat", torch.float32)
+    if feat.dim() != 2 or (first is None) != (prev is None):
+        raise ValueError("feature_consistency: expected feat [F, D] and both carried rows or neither")
+    F, D = feat.shape
+    for t, name in ((first, "first"), (prev, "prev")):
+        if t is not None and (_chk(t, name, torch.float32).numel() != D or not t.is_contiguous()):
+            raise ValueError(f"feature_consistency: {name} must be a contiguous row of {D} elements, got {tuple(t.shape)}")
+    n = F if first is not None else F - 1
+    if n < 1:
+        raise ValueError(f"feature_consistency: no frame with a predecessor among {F}")
+    out = torch.empty(2, n, dtype=torch.float64, device=feat.device)
+    L.check(_launch("feature_consistency", L.load().tg_feature_consistency, _p(feat), feat.stride(0), F, D, _p(first), _p(prev), _p(out[0]), _p(out[1]), _stream()),
+            "tg_feature_consistency")
+    return out[0], out[1]

@@ -87,6 +87,11 @@ PROTOTYPES = {
     "tg_t5_attention": [_vp, _vp, _vp, _l, _l, _vp, _vp, _i, _i, _i, _vp],
     "tg_gated_gelu": [_vp, _l, _vp, _l, _l, _i, _vp],
     "tg_residual_add": [_vp, _vp, _vp, _l, _vp],
+    "tg_vit_patch_rows": [_vp, _i, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _vp, _i, _vp],
+    "tg_vit_assemble": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "tg_layernorm": [_vp, _l, _vp, _vp, _vp, _l, _l, _i, _f, _vp],
+    "tg_vit_act": [_vp, _vp, _l, _i, _vp],
+    "tg_feature_consistency": [_vp, _l, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "tg_conv3d_cl": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _l, _i, _i, _i, _vp, _vp, _vp, _vp],
     "tg_conv3d_up2_subpixel": [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _l, _i, _vp, _vp, _vp],
     "tg_groupnorm_finalize": [_vp, _l, _i, _f, _vp, _vp],

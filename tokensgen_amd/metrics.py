@@ -14,6 +14,10 @@ absent here).  STATED DEVIATION: with `test_y_channel` the reference forms Y in 
 `calculate_lpips` keeps the signature of longvgen/metrics/lpips.py:12-47 (`model(img2, img)`) for a tokensgen_amd.lpips.LPIPS model; `VideoMetrics(lpips_model=...)`
 carries LPIPS next to the other two (tokensgen_amd/lpips.py).
 
+`video_consistency` / `VideoConsistency` need no second video: a frozen image encoder (tokensgen_amd.vit.ViTEncoder) embeds every frame, and each frame's feature is
+compared by cosine similarity with the previous frame's and with the first frame's (tg_feature_consistency, csrc/vit.hip) — the subject (DINO ViT-B/16) and
+background (CLIP ViT-B/32) consistency of the common video benchmarks, the figure for the generated, source-less videos of the gen path.
+
 Not here: `calculate_delta_Eab` (cv2.cvtColor's 8-bit Lab, source absent), the numpy / skimage variants.  Not registered under the `longvgen`
 alias (tokensgen_amd.compat carries hot-path names only).  There is no CPU path."""
 import torch
@@ -117,4 +121,70 @@ class VideoMetrics:
         if self.lpips_model is not None:
             out["lpips"] = torch.cat(self._lpips)
             out["lpips_pooled"] = out["lpips"].mean()
+        return out
+
+
+def video_consistency(frames, model):
+    """Frame consistency of ONE video under a frozen image encoder.  frames: what model.encode_frames takes (uint8 [F, H, W, 3] / [B, T, H, W, 3] display frames, or
+    bf16 [F, 3, s, s] in [-1, 1]), n >= 2 of them; model: a tokensgen_amd.vit.ViTEncoder.  Returns float64 device tensors: "prev" [n - 1] = max(0, cos(f_i, f_{i-1})),
+    "first" [n - 1] = max(0, cos(f_i, f_0)) for i = 1 .. n - 1, and the 0-dim "score" = mean((prev + first) / 2).  Nothing here waits for the device."""
+    n = frames.shape[0] * frames.shape[1] if (frames.dtype == torch.uint8 and frames.dim() == 5) else frames.shape[0]
+    if n < 2:
+        raise ValueError(f"video_consistency: a video of {n} frame(s) has no frame with a predecessor; pass at least 2")
+    prev, first = K.feature_consistency(model.encode_frames(frames))
+    return {"prev": prev, "first": first, "score": ((prev + first) / 2).mean()}
+
+
+class VideoConsistency:
+    """Streaming frame consistency of long videos that arrive clip by clip (the FIFO driver hands out 25 clips of one 1 200-frame video).
+    `update(frames)` continues the current video: it embeds the clip with every attached model and keeps, per model, the video's first and last feature on the
+    device; `new_video()` closes the current video; `finalize()` closes it too and returns, per attached model <name> in ("subject", "background"):
+    "<name>_scores" float64 [videos], "<name>_consistency" their mean (0-dim), "<name>_first" and "<name>_prev": one float64 [n_v - 1] curve per video — `first` is
+    the drift against the opening frame over the whole video.  Feeding a video in pieces gives the bits of feeding it whole.  Nothing waits for the device."""
+
+    def __init__(self, subject_model=None, background_model=None):
+        self.models = {k: m for k, m in (("subject", subject_model), ("background", background_model)) if m is not None}
+        if not self.models:
+            raise ValueError("VideoConsistency: attach a subject_model and / or a background_model (tokensgen_amd.vit.ViTEncoder)")
+        self._videos = {k: [] for k in self.models}              # closed videos: (prev curve, first curve)
+        self._open = {k: None for k in self.models}              # the current video: dict(first, last, prev=[...], firsts=[...], frames)
+
+    def update(self, frames):
+        out = {}
+        for name, model in self.models.items():
+            feats = model.encode_frames(frames)
+            st = self._open[name]
+            if st is None:
+                st = self._open[name] = {"first": feats[0].clone(), "last": None, "prev": [], "firsts": [], "frames": 0}
+                pair = K.feature_consistency(feats) if feats.shape[0] >= 2 else None
+            else:
+                pair = K.feature_consistency(feats, st["first"], st["last"])
+            if pair is not None:
+                st["prev"].append(pair[0])
+                st["firsts"].append(pair[1])
+            st["last"] = feats[-1].clone()
+            st["frames"] += feats.shape[0]
+            out[name] = pair
+        return out
+
+    def new_video(self):
+        for name in self.models:
+            st = self._open[name]
+            if st is None:
+                continue
+            if st["frames"] < 2:
+                raise ValueError(f"VideoConsistency: the current video has {st['frames']} frame(s); a video needs at least 2")
+            self._videos[name].append((torch.cat(st["prev"]), torch.cat(st["firsts"])))
+            self._open[name] = None
+
+    def finalize(self):
+        self.new_video()
+        out = {}
+        for name in self.models:
+            vids = self._videos[name]
+            if not vids:
+                raise RuntimeError("VideoConsistency.finalize: no update yet")
+            scores = torch.stack([((p + f) / 2).mean() for p, f in vids])
+            out.update({f"{name}_scores": scores, f"{name}_consistency": scores.mean(), f"{name}_prev": [p for p, _ in vids], f"{name}_first": [f for _, f in vids]})
+        out["videos"] = len(next(iter(self._videos.values())))
         return out
