@@ -834,6 +834,24 @@ int tg_vit_act(const void* x, void* y, long n, int mode, hipStream_t stream);
 int tg_feature_consistency(const float* feat, long ld, int F, int D, const float* first_row, const float* prev_row, double* prev_out, double* first_out,
                            hipStream_t stream);
 
+/* The CLIP text tower and the text-video alignment on its features (csrc/clip_text.hip; host side: tokensgen_amd/clip_text.py and metrics.py):
+ * transformers' CLIPTextModelWithProjection, a pre-LayerNorm transformer with heads of 64 and CAUSAL self-attention.  Every projection is tg_gemm_bf16 with
+ * TG_EPI_BIAS; the norms are tg_layernorm, the activation tg_vit_act, the residual tg_residual_add; the attention is tg_t5_attention with q_proj pre-scaled by 1/8 at
+ * load and a bias_by_distance table of 0 for j - i <= 0 and -inf for j - i > 0 (key 0 is visible to every query, so every row maximum is finite and a masked term is
+ * exp(-inf) = 0 exactly).  These two exports are the rest.
+ * tg_text_embed: out[r][:] = bf16( fp32(tok_emb[ids[r]][:]) + fp32(pos_emb[r % S][:]) ), one rounding — `token_embedding(input_ids) + position_embedding(position_ids)`
+ *   of CLIPTextEmbeddings (the host `nn.Embedding` gather and add).  ids: int32 [rows], rows = B * S; tok_emb bf16 [V][D], pos_emb bf16 [>= S][D], both contiguous;
+ *   out bf16 [rows][D] with row stride ldo; D % 8 == 0; tok_emb, pos_emb, out 16-byte aligned, ldo a multiple of 8.  An id outside [0, V) is never used as an index:
+ *   its row is written as zeros and the caller-owned DEVICE word status[0] is incremented by one (the caller zeroes it; the convention of tg_attention_bwd_ex's
+ *   status words).  The Python side validates the ids on the host first, so a non-zero status means a caller that skipped that.
+ * tg_text_alignment: cos_out[f][k] = x_f . y_k / (max(|x_f|, 1e-8) * max(|y_k|, 1e-8)) in float64 — torch.nn.functional.cosine_similarity of image feature
+ *   x_f = img[f] (fp32 [F][D], row stride ld_img) and text feature y_k = txt[k] (fp32 [K][D], row stride ld_txt); NOT clamped at 0 (metrics.video_text_alignment
+ *   clamps when it averages).  Any F >= 1, K >= 1, D >= 1.  One wave per frame, all sums float64 in a fixed order, no atomics: bitwise reproducible, and an output
+ *   depends on its two rows alone, so a video fed in pieces gives the bits of the video fed whole.  A zero row gives 0, not NaN.  Features 4-byte aligned,
+ *   cos_out (float64 [F][K], contiguous) 8-byte aligned. */
+int tg_text_embed(const int* ids, long rows, int S, const void* tok_emb, int V, const void* pos_emb, void* out, long ldo, int D, int* status, hipStream_t stream);
+int tg_text_alignment(const float* img, long ld_img, int F, const float* txt, long ld_txt, int K, int D, double* cos_out, hipStream_t stream);
+
 /* Dispatch overrides for the cross-check tests — NOT part of the operator surface.  The library reads no environment variable and keeps no other
  * process-wide state: the defaults are the shipped path, and these knobs only choose between two PRODUCT kernels of the same operator (each pair is held
  * bitwise or to rounding against each other by tests/).  Knobs: TG_ATTN_PP_MIN_WG (1024: workgroups from which the 8-wave attention kernel is used),

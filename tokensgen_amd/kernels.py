@@ -1169,3 +1169,32 @@ def feature_consistency(feat, first=None, prev=None):
     L.check(_launch("feature_consistency", L.load().tg_feature_consistency, _p(feat), feat.stride(0), F, D, _p(first), _p(prev), _p(out[0]), _p(out[1]), _stream()),
             "tg_feature_consistency")
     return out[0], out[1]
+
+
+def text_embed(ids, seq, tok_emb, pos_emb, out, status):
+    """tg_text_embed: out[r] = bf16(tok_emb[ids[r]] + pos_emb[r % seq]) for the int32 ids [rows] (rows a multiple of seq); tok_emb bf16 [V, D], pos_emb bf16 [>= seq, D],
+    out bf16 [>= rows, D] with a row stride, status int32 [1] on the device: incremented once per id outside [0, V), whose row is written as zeros."""
+    _chk(ids, "ids", torch.int32); _chk(tok_emb, "tok_emb"); _chk(pos_emb, "pos_emb"); _chk(out, "out"); _chk(status, "status", torch.int32)
+    rows = ids.numel()
+    if ids.dim() != 1 or rows < 1 or seq < 1 or rows % seq or tok_emb.dim() != 2 or pos_emb.dim() != 2 or out.dim() != 2 or status.numel() != 1:
+        raise ValueError(f"text_embed: expected ids [rows] with rows a multiple of seq = {seq}, tok_emb [V, D], pos_emb [P, D], out [>= rows, D] and status [1]; got "
+                         f"{tuple(ids.shape)}, {tuple(tok_emb.shape)}, {tuple(pos_emb.shape)}, {tuple(out.shape)}, {tuple(status.shape)}")
+    V, D = tok_emb.shape
+    if pos_emb.shape[0] < seq or pos_emb.shape[1] != D or out.shape[1] != D or out.shape[0] < rows or not (tok_emb.is_contiguous() and pos_emb.is_contiguous()):
+        raise ValueError(f"text_embed: tok_emb{tuple(tok_emb.shape)} needs contiguous pos_emb [>= {seq}, {D}] and out [>= {rows}, {D}]; got {tuple(pos_emb.shape)} and "
+                         f"{tuple(out.shape)}")
+    L.check(_launch("text_embed", L.load().tg_text_embed, _p(ids), rows, int(seq), _p(tok_emb), V, _p(pos_emb), _p(out), out.stride(0), D, _p(status), _stream()),
+            "tg_text_embed")
+    return out
+
+
+def text_alignment(img, txt):
+    """tg_text_alignment: img fp32 [F, D], txt fp32 [K, D] (row strides allowed) -> float64 [F, K]: cos(img[f], txt[k]) = x . y / (max(|x|, 1e-8) max(|y|, 1e-8)),
+    not clamped.  Bitwise reproducible; an output depends on its two rows alone."""
+    _chk(img, "img", torch.float32); _chk(txt, "txt", torch.float32)
+    if img.dim() != 2 or txt.dim() != 2 or img.shape[1] != txt.shape[1] or img.shape[0] < 1 or txt.shape[0] < 1:
+        raise ValueError(f"text_alignment: expected img [F, D] and txt [K, D] of one width, got {tuple(img.shape)} and {tuple(txt.shape)}")
+    (F, D), Kt = img.shape, txt.shape[0]
+    out = torch.empty(F, Kt, dtype=torch.float64, device=img.device)
+    L.check(_launch("text_alignment", L.load().tg_text_alignment, _p(img), img.stride(0), F, _p(txt), txt.stride(0), Kt, D, _p(out), _stream()), "tg_text_alignment")
+    return out

@@ -92,6 +92,8 @@ PROTOTYPES = {
     "tg_layernorm": [_vp, _l, _vp, _vp, _vp, _l, _l, _i, _f, _vp],
     "tg_vit_act": [_vp, _vp, _l, _i, _vp],
     "tg_feature_consistency": [_vp, _l, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "tg_text_embed": [_vp, _l, _i, _vp, _i, _vp, _vp, _l, _i, _vp, _vp],
+    "tg_text_alignment": [_vp, _l, _i, _vp, _l, _i, _i, _vp, _vp],
     "tg_conv3d_cl": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _l, _i, _i, _i, _vp, _vp, _vp, _vp],
     "tg_conv3d_up2_subpixel": [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _l, _i, _vp, _vp, _vp],
     "tg_groupnorm_finalize": [_vp, _l, _i, _f, _vp, _vp],

@@ -18,6 +18,10 @@ carries LPIPS next to the other two (tokensgen_amd/lpips.py).
 compared by cosine similarity with the previous frame's and with the first frame's (tg_feature_consistency, csrc/vit.hip) — the subject (DINO ViT-B/16) and
 background (CLIP ViT-B/32) consistency of the common video benchmarks, the figure for the generated, source-less videos of the gen path.
 
+`video_text_alignment` says whether a video shows what its prompt asks for: the cosine of every frame's CLIP image feature with the CLIP text feature of each of K
+texts (tokensgen_amd.clip_text.CLIPTextEncoder; tg_text_alignment, csrc/clip_text.hip) — CLIPSIM / CLIP-T.  `VideoConsistency(text_features=...)` carries it on
+the background model's features, which are computed once per clip either way.
+
 Not here: `calculate_delta_Eab` (cv2.cvtColor's 8-bit Lab, source absent), the numpy / skimage variants.  Not registered under the `longvgen`
 alias (tokensgen_amd.compat carries hot-path names only).  There is no CPU path."""
 import torch
@@ -135,24 +139,74 @@ def video_consistency(frames, model):
     return {"prev": prev, "first": first, "score": ((prev + first) / 2).mean()}
 
 
+def _text_features(text_features, image_model, who):
+    """fp32 [K, D] or [D] -> [K, D] on the image model's device, checked against the image tower"""
+    if getattr(image_model, "kind", None) != "clip":
+        raise ValueError(f"{who}: text features live in CLIP's joint space: the image model must be a tokensgen_amd.vit.ViTEncoder(kind='clip')")
+    if not isinstance(text_features, torch.Tensor) or text_features.dtype != torch.float32 or text_features.dim() not in (1, 2):
+        raise TypeError(f"{who}: text_features must be an fp32 tensor [K, D] or [D] (clip_text.CLIPTextEncoder.encode_text)")
+    t = text_features[None] if text_features.dim() == 1 else text_features
+    if t.shape[0] < 1 or t.shape[1] != image_model.out_dim:
+        raise ValueError(f"{who}: text features of width {t.shape[1]} ({t.shape[0]} texts), the image tower projects to {image_model.out_dim}: the two towers must "
+                         "come from one CLIP model")
+    return t.to(image_model.device)
+
+
+def _alignment_scores(cos):
+    """cos float64 [F, K] -> (per_text [K] = mean over frames of max(0, cos), score = their mean)"""
+    per_text = cos.clamp_min(0.0).mean(dim=0)
+    return per_text, per_text.mean()
+
+
+def video_text_alignment(frames, image_model, text_features):
+    """How well ONE video shows what K texts say, under a CLIP model: the cosine between every frame's image feature and every text's feature (CLIPSIM / CLIP-T).
+    frames: what video_consistency takes, n >= 1 of them; image_model: a tokensgen_amd.vit.ViTEncoder(kind="clip"); text_features: fp32 [K, D] or [D] from the same
+    CLIP model's text tower (clip_text.CLIPTextEncoder.encode_text), D == image_model.out_dim.  Returns float64 device tensors: "cos" [F, K] (tg_text_alignment,
+    not clamped), "per_text" [K] = the mean over frames of max(0, cos), and the 0-dim "score" = mean(per_text).  Hessel et al.'s CLIPScore is 2.5 x this value per
+    frame, and the figure usually reported as "CLIPSIM" is 100 x it.  K texts exist for long prompts: encode a paragraph sentence by sentence (CLIP reads 77 tokens)
+    and read one curve per sentence from `cos`; any aggregation beyond per_text / score is the caller's.  Nothing here waits for the device."""
+    txt = _text_features(text_features, image_model, "video_text_alignment")
+    cos = K.text_alignment(image_model.encode_frames(frames), txt)
+    per_text, score = _alignment_scores(cos)
+    return {"cos": cos, "per_text": per_text, "score": score}
+
+
 class VideoConsistency:
     """Streaming frame consistency of long videos that arrive clip by clip (the FIFO driver hands out 25 clips of one 1 200-frame video).
     `update(frames)` continues the current video: it embeds the clip with every attached model and keeps, per model, the video's first and last feature on the
     device; `new_video()` closes the current video; `finalize()` closes it too and returns, per attached model <name> in ("subject", "background"):
     "<name>_scores" float64 [videos], "<name>_consistency" their mean (0-dim), "<name>_first" and "<name>_prev": one float64 [n_v - 1] curve per video — `first` is
-    the drift against the opening frame over the whole video.  Feeding a video in pieces gives the bits of feeding it whole.  Nothing waits for the device."""
+    the drift against the opening frame over the whole video.  Feeding a video in pieces gives the bits of feeding it whole.  Nothing waits for the device.
 
-    def __init__(self, subject_model=None, background_model=None):
+    Text alignment rides on the background model's features: with `text_features` (fp32 [K, D] or [D], clip_text.CLIPTextEncoder.encode_text; the constructor's for the
+    first video, `new_video(text_features=...)` for the next) and a CLIP background_model, the frames' features — computed ONCE per clip, as without it — also go
+    through tg_text_alignment (`update` hands that clip's float64 [n, K] back as "text_cos"), and `finalize()` additionally returns "text_cos": one float64 [n_v, K_v] curve per video (None for a video without text features),
+    "text_alignment" float64 [videos] = video_text_alignment's score per video (NaN for a video without), and "text_alignment_mean", the mean over the videos that
+    have one.  With no text features anywhere every key, value and launch is what it was."""
+
+    def __init__(self, subject_model=None, background_model=None, text_features=None):
         self.models = {k: m for k, m in (("subject", subject_model), ("background", background_model)) if m is not None}
         if not self.models:
             raise ValueError("VideoConsistency: attach a subject_model and / or a background_model (tokensgen_amd.vit.ViTEncoder)")
         self._videos = {k: [] for k in self.models}              # closed videos: (prev curve, first curve)
         self._open = {k: None for k in self.models}              # the current video: dict(first, last, prev=[...], firsts=[...], frames)
+        self._text = self._check_text(text_features)             # the current video's text features [K, D], or None
+        self._text_cos, self._text_videos, self._any_text = [], [], self._text is not None
+
+    def _check_text(self, text_features):
+        if text_features is None:
+            return None
+        if "background" not in self.models:
+            raise ValueError("VideoConsistency: text features need a CLIP background_model (tokensgen_amd.vit.ViTEncoder(kind='clip'))")
+        return _text_features(text_features, self.models["background"], "VideoConsistency")
 
     def update(self, frames):
         out = {}
         for name, model in self.models.items():
             feats = model.encode_frames(frames)
+            if name == "background" and self._text is not None:
+                self._text_cos.append(K.text_alignment(feats, self._text))
+                out["text_cos"] = self._text_cos[-1]
             st = self._open[name]
             if st is None:
                 st = self._open[name] = {"first": feats[0].clone(), "last": None, "prev": [], "firsts": [], "frames": 0}
@@ -167,7 +221,10 @@ class VideoConsistency:
             out[name] = pair
         return out
 
-    def new_video(self):
+    def new_video(self, text_features=None):
+        """Closes the current video; the next one is compared with `text_features` (None: it has no text alignment)."""
+        nxt = self._check_text(text_features)
+        closed = False
         for name in self.models:
             st = self._open[name]
             if st is None:
@@ -176,9 +233,24 @@ class VideoConsistency:
                 raise ValueError(f"VideoConsistency: the current video has {st['frames']} frame(s); a video needs at least 2")
             self._videos[name].append((torch.cat(st["prev"]), torch.cat(st["firsts"])))
             self._open[name] = None
+            closed = True
+        if closed:
+            self._text_videos.append(torch.cat(self._text_cos) if self._text_cos else None)
+        self._text, self._text_cos = nxt, []
+        self._any_text = self._any_text or nxt is not None
 
     def finalize(self):
         self.new_video()
+        out = self._finalize_consistency()
+        if self._any_text:
+            dev = self.models["background"].device
+            scores = [_alignment_scores(c)[1] if c is not None else torch.full((), float("nan"), dtype=torch.float64, device=dev) for c in self._text_videos]
+            have = [s for s, c in zip(scores, self._text_videos) if c is not None]
+            out.update({"text_cos": list(self._text_videos), "text_alignment": torch.stack(scores),
+                        "text_alignment_mean": torch.stack(have).mean() if have else torch.full((), float("nan"), dtype=torch.float64, device=dev)})
+        return out
+
+    def _finalize_consistency(self):
         out = {}
         for name in self.models:
             vids = self._videos[name]
