@@ -852,6 +852,33 @@ int tg_feature_consistency(const float* feat, long ld, int F, int D, const float
 int tg_text_embed(const int* ids, long rows, int S, const void* tok_emb, int V, const void* pos_emb, void* out, long ldo, int D, int* status, hipStream_t stream);
 int tg_text_alignment(const float* img, long ld_img, int F, const float* txt, long ld_txt, int K, int D, double* cos_out, hipStream_t stream);
 
+/* Motion between the frames of a video, in integers (csrc/motion.hip; host side: tokensgen_amd/motion.py and metrics.py).  No reference code: these
+ * are the definitions.
+ * Luma: Y = (77 R + 150 G + 29 B + 128) >> 8 of uint8 RGB, 0 .. 255 (77 + 150 + 29 = 256).
+ * Blocks: block in {8, 16}; blocks tile the plane from the top left, Hb = H / block, Wb = W / block (integer division); trailing rows / columns narrower than a block
+ *   belong to no block.  H, W >= block.
+ * Candidates of the block at (y, x) for radius R (1 <= R <= 32): every integer (dy, dx), |dy|, |dx| <= R, with 0 <= y + dy, y + dy + block <= H, 0 <= x + dx,
+ *   x + dx + block <= W.  No padding; (0, 0) is always a candidate.
+ * Cost: sad(dy, dx) = sum_{i,j < block} |Y_cur[y + i][x + j] - Y_ref[y + dy + i][x + dx + j]|.  The winner is the minimum of (sad, dy^2 + dx^2, dy, dx) in lexicographic
+ *   order, dy and dx signed: flat regions give (0, 0), periodic textures the shortest vector, and the result depends on no order of evaluation.
+ * tg_luma_u8: dst[(outer * n_inner + inner)][y][x] = Y of the pixel whose channel c is byte src[outer * so + inner * si + y * sr + x * sp + c * sc] (strides >= 0:
+ *   interleaved [.., H, W, 3] has sp = 3, sc = 1; a crop is a base offset with a smaller H, W).  dst: planes of H rows of tg_luma_pitch(W) bytes (W rounded up to a
+ *   multiple of 4; the pad bytes are written as 0), 4-byte aligned.
+ * tg_block_motion: for pair (o, i), o < n_outer, i < n_inner, the blocks of luma plane cur + o * cur_so + i * cur_si are searched in plane ref + o * ref_so + i * ref_si
+ *   (byte strides, multiples of 4; both planes H rows of `pitch` bytes, pitch % 4 == 0, pitch >= W).  Outputs, contiguous over [n_outer][n_inner][Hb][Wb]: mv int16
+ *   [..][2] = (dy, dx), "the block at (y, x) of cur matches (y + dy, x + dx) of ref"; sad int32, the winner's cost; sad0 int32, the cost at (0, 0).  One launch, no
+ *   atomics, bitwise reproducible; a block's result depends on its pair's two planes alone.
+ * tg_block_warp_sse: for the same pairs and blocks on uint8 RGB (strides as tg_luma_u8, per input) and vectors mv (int16 [n_outer][n_inner][Hb][Wb][2]):
+ *   sse = sum_{i,j,c} (cur[y + i][x + j][c] - ref[y + dy + i][x + dx + j][c])^2 and sse0 the same at zero displacement, int32 (at most 16 * 16 * 3 * 255^2 < 2^31).
+ *   A vector that would take its block out of the frame is never used as an address: the displaced origin is clamped to [0, H - block] x [0, W - block] and the
+ *   caller-owned DEVICE word status[0] is incremented by one (the caller zeroes it; the convention of tg_text_embed). */
+long tg_luma_pitch(int W);
+int tg_luma_u8(const void* src, long so, long si, long sr, long sp, long sc, int n_outer, int n_inner, int H, int W, void* dst, hipStream_t stream);
+int tg_block_motion(const void* cur, long cur_so, long cur_si, const void* ref, long ref_so, long ref_si, int n_outer, int n_inner, int H, int W, long pitch, int block,
+                    int radius, void* mv, void* sad, void* sad0, hipStream_t stream);
+int tg_block_warp_sse(const void* cur, long a_so, long a_si, long a_sr, long a_sp, long a_sc, const void* ref, long b_so, long b_si, long b_sr, long b_sp, long b_sc,
+                      const void* mv, int n_outer, int n_inner, int H, int W, int block, void* sse, void* sse0, int* status, hipStream_t stream);
+
 /* Dispatch overrides for the cross-check tests — NOT part of the operator surface.  The library reads no environment variable and keeps no other
  * process-wide state: the defaults are the shipped path, and these knobs only choose between two PRODUCT kernels of the same operator (each pair is held
  * bitwise or to rounding against each other by tests/).  Knobs: TG_ATTN_PP_MIN_WG (1024: workgroups from which the 8-wave attention kernel is used),

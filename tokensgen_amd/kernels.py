@@ -1198,3 +1198,73 @@ def text_alignment(img, txt):
     out = torch.empty(F, Kt, dtype=torch.float64, device=img.device)
     L.check(_launch("text_alignment", L.load().tg_text_alignment, _p(img), img.stride(0), F, _p(txt), txt.stride(0), Kt, D, _p(out), _stream()), "tg_text_alignment")
     return out
+
+
+MOTION_BLOCKS, MOTION_MAX_RADIUS = (8, 16), 32
+
+
+def _rgb_strides(t):
+    """(n_outer, n_inner, H, W) and the byte strides (outer, inner, row, pixel, channel) of uint8 [F, H, W, 3] / [B, T, H, W, 3] frames (any view)"""
+    s = t.stride()
+    if t.dim() == 4:
+        return (1, t.shape[0], t.shape[1], t.shape[2]), (0, s[0], s[1], s[2], s[3])
+    return (t.shape[0], t.shape[1], t.shape[2], t.shape[3]), (s[0], s[1], s[2], s[3], s[4])
+
+
+def _chk_frames(t, name):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{name}: expected a GPU tensor (tokensgen_amd has no CPU fallback)")
+    if t.dtype != torch.uint8 or t.dim() not in (4, 5) or t.shape[-1] != 3 or min(t.stride()) < 0:
+        raise ValueError(f"{name}: expected uint8 [F, H, W, 3] or [B, T, H, W, 3] with non-negative strides, got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def luma_u8(frames):
+    """tg_luma_u8: uint8 RGB frames [F, H, W, 3] / [B, T, H, W, 3] (any view) -> uint8 luma planes [n_outer, n_inner, H, pitch], pitch = W rounded up to a multiple of
+    4 (pad bytes 0); Y = (77 R + 150 G + 29 B + 128) >> 8."""
+    _chk_frames(frames, "frames")
+    (no, ni, H, W), st = _rgb_strides(frames)
+    if no * ni < 1 or H < 1 or W < 1:
+        raise ValueError(f"luma_u8: no pixels in {tuple(frames.shape)}")
+    lib = L.load()
+    out = torch.empty(no, ni, H, lib.tg_luma_pitch(W), dtype=torch.uint8, device=frames.device)
+    L.check(_launch("luma_u8", lib.tg_luma_u8, _p(frames), *st, no, ni, H, W, _p(out), _stream()), "tg_luma_u8")
+    return out
+
+
+def block_motion(cur, ref, width, block, radius):
+    """tg_block_motion: cur, ref uint8 luma planes [n_outer, n_inner, H, pitch] from luma_u8 (views along the first two axes allowed: a video's planes 0 .. T - 2 and
+    1 .. T - 1), width = the planes' true W.  Returns mv int16 [n_outer, n_inner, Hb, Wb, 2] (dy, dx), sad and sad0 int32 [n_outer, n_inner, Hb, Wb]."""
+    for t, name in ((cur, "cur"), (ref, "ref")):
+        _chk(t, name, torch.uint8)
+    if cur.dim() != 4 or cur.shape != ref.shape or cur.stride()[2:] != (cur.shape[3], 1) or ref.stride()[2:] != (ref.shape[3], 1):
+        raise ValueError(f"block_motion: expected two equally shaped stacks of packed planes [n_outer, n_inner, H, pitch], got {tuple(cur.shape)} and {tuple(ref.shape)}")
+    no, ni, H, pitch = cur.shape
+    block, radius, W = int(block), int(radius), int(width)
+    if block not in MOTION_BLOCKS or not 1 <= radius <= MOTION_MAX_RADIUS or no * ni < 1 or not block <= W <= pitch or H < block:
+        raise ValueError(f"block_motion: block {block} (8 or 16), radius {radius} (1..{MOTION_MAX_RADIUS}), planes {tuple(cur.shape)} of width {W}")
+    Hb, Wb = H // block, W // block
+    mv = torch.empty(no, ni, Hb, Wb, 2, dtype=torch.int16, device=cur.device)
+    sad = torch.empty(2, no, ni, Hb, Wb, dtype=torch.int32, device=cur.device)
+    L.check(_launch("block_motion", L.load().tg_block_motion, _p(cur), cur.stride(0), cur.stride(1), _p(ref), ref.stride(0), ref.stride(1), no, ni, H, W, pitch, block,
+                    radius, _p(mv), _p(sad[0]), _p(sad[1]), _stream()), "tg_block_motion")
+    return mv, sad[0], sad[1]
+
+
+def block_warp_sse(cur, ref, mv, block):
+    """tg_block_warp_sse: cur, ref uint8 RGB frames of one shape ([F, H, W, 3] / [B, T, H, W, 3], any views), pair i of cur against pair i of ref; mv int16
+    [n_outer, n_inner, Hb, Wb, 2] contiguous.  Returns sse, sse0 int32 [n_outer, n_inner, Hb, Wb] and status int32 [1] (vectors that had to be clamped)."""
+    _chk_frames(cur, "cur"); _chk_frames(ref, "ref"); _chk(mv, "mv", torch.int16)
+    (no, ni, H, W), sa = _rgb_strides(cur)
+    _, sb = _rgb_strides(ref)
+    block = int(block)
+    if cur.shape != ref.shape or block not in MOTION_BLOCKS or no * ni < 1 or H < block or W < block:
+        raise ValueError(f"block_warp_sse: frames {tuple(cur.shape)} and {tuple(ref.shape)} with block {block}")
+    Hb, Wb = H // block, W // block
+    if tuple(mv.shape) != (no, ni, Hb, Wb, 2) or not mv.is_contiguous():
+        raise ValueError(f"block_warp_sse: mv must be contiguous [{no}, {ni}, {Hb}, {Wb}, 2], got {tuple(mv.shape)}")
+    sse = torch.empty(2, no, ni, Hb, Wb, dtype=torch.int32, device=cur.device)
+    status = torch.zeros(1, dtype=torch.int32, device=cur.device)
+    L.check(_launch("block_warp_sse", L.load().tg_block_warp_sse, _p(cur), *sa, _p(ref), *sb, _p(mv), no, ni, H, W, block, _p(sse[0]), _p(sse[1]), _p(status),
+                    _stream()), "tg_block_warp_sse")
+    return sse[0], sse[1], status

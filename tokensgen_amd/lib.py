@@ -94,6 +94,9 @@ PROTOTYPES = {
     "tg_feature_consistency": [_vp, _l, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "tg_text_embed": [_vp, _l, _i, _vp, _i, _vp, _vp, _l, _i, _vp, _vp],
     "tg_text_alignment": [_vp, _l, _i, _vp, _l, _i, _i, _vp, _vp],
+    "tg_luma_u8": [_vp, _l, _l, _l, _l, _l, _i, _i, _i, _i, _vp, _vp],
+    "tg_block_motion": [_vp, _l, _l, _vp, _l, _l, _i, _i, _i, _i, _l, _i, _i, _vp, _vp, _vp, _vp],
+    "tg_block_warp_sse": [_vp, _l, _l, _l, _l, _l, _vp, _l, _l, _l, _l, _l, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
     "tg_conv3d_cl": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _l, _i, _i, _i, _vp, _vp, _vp, _vp],
     "tg_conv3d_up2_subpixel": [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _l, _i, _vp, _vp, _vp],
     "tg_groupnorm_finalize": [_vp, _l, _i, _f, _vp, _vp],
@@ -136,6 +139,7 @@ QUERIES = {
     "tg_image_metrics_tile": [C.c_int],
     "tg_image_metrics_ws_doubles": [C.c_long, C.c_int, C.c_int],
     "tg_lpips_head_ws_doubles": [C.c_int, C.c_int, C.c_int],
+    "tg_luma_pitch": [C.c_int],
 }
 
 TG_BWD_ONE_KERNEL = 1

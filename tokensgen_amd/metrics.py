@@ -22,11 +22,16 @@ background (CLIP ViT-B/32) consistency of the common video benchmarks, the figur
 texts (tokensgen_amd.clip_text.CLIPTextEncoder; tg_text_alignment, csrc/clip_text.hip) — CLIPSIM / CLIP-T.  `VideoConsistency(text_features=...)` carries it on
 the background model's features, which are computed once per clip either way.
 
-Not here: `calculate_delta_Eab` (cv2.cvtColor's 8-bit Lab, source absent), the numpy / skimage variants.  Not registered under the `longvgen`
+`video_motion` / `video_warp_error` / `VideoMotion` measure what the figures above do not, motion: exhaustive integer block matching on 8-bit luma
+(tokensgen_amd.motion; tg_block_motion, csrc/motion.hip) gives per frame pair the motion magnitude, its top-fraction mean ("dynamic degree"), the share of still
+blocks, flicker and the motion-compensated residual, and the warping error of a video under its own vectors or under those of an edit's source.
+
+Not here: `calculate_delta_Eab` (cv2.cvtColor's 8-bit Lab, source absent), the numpy / skimage variants, learned optical flow.  Not registered under the `longvgen`
 alias (tokensgen_amd.compat carries hot-path names only).  There is no CPU path."""
 import torch
 
 from . import kernels as K
+from . import motion as M
 
 WINDOW = K.IMAGE_WINDOW
 
@@ -259,4 +264,124 @@ class VideoConsistency:
             scores = torch.stack([((p + f) / 2).mean() for p, f in vids])
             out.update({f"{name}_scores": scores, f"{name}_consistency": scores.mean(), f"{name}_prev": [p for p, _ in vids], f"{name}_first": [f for _, f in vids]})
         out["videos"] = len(next(iter(self._videos.values())))
+        return out
+
+
+MOTION_CURVES = ("magnitude", "magnitude_top", "static_fraction", "flicker", "residual")
+WARP_CURVES = ("warp_mse", "warp_psnr", "still_mse", "still_psnr")
+
+
+def _psnr(mse):
+    return 10.0 * torch.log10(1.0 / (mse + 1e-8))
+
+
+def _motion_curves(frames, block, radius, top_fraction):
+    r = M.block_motion(frames, block, radius)
+    return M.summarize(r["mv"], r["sad"], r["sad0"], block, top_fraction), r
+
+
+def video_motion(frames, block=16, radius=16, top_fraction=0.05):
+    """How much a video moves, from integer block matching between consecutive frames (motion.block_motion).  frames: uint8 [F, H, W, 3] or [B, T, H, W, 3], at least 2
+    frames.  Returns float64 device tensors: the per-pair curves of motion.summarize — "magnitude", "magnitude_top", "static_fraction", "flicker", "residual" — shaped
+    [F - 1] / [B, T - 1], and "<curve>_mean", their 0-dim means over all pairs.  A near-still video has magnitude 0 and static_fraction 1 whatever its consistency
+    scores say; a jump at a clip join shows as a spike of `residual`.  Nothing here waits for the device."""
+    M.check_frames(frames, "video_motion")
+    M.check_block(block, radius, frames.shape[-3], frames.shape[-2], "video_motion")
+    M.top_count(top_fraction, 1)
+    out, _ = _motion_curves(frames, block, radius, top_fraction)
+    out.update({f"{k}_mean": out[k].mean() for k in MOTION_CURVES})
+    return out
+
+
+def _warp_curves(sse, sse0, block):
+    norm = 3.0 * sse.shape[-2] * sse.shape[-1] * block * block * 255.0 * 255.0
+    mse = sse.flatten(-2).sum(-1, dtype=torch.int64).to(torch.float64) / norm
+    still = sse0.flatten(-2).sum(-1, dtype=torch.int64).to(torch.float64) / norm
+    return {"warp_mse": mse, "warp_psnr": _psnr(mse), "still_mse": still, "still_psnr": _psnr(still)}
+
+
+def _warp_pooled(out):
+    out.update({"warp_mse_mean": out["warp_mse"].mean(), "warp_psnr_pooled": _psnr(out["warp_mse"].mean()), "still_mse_mean": out["still_mse"].mean(),
+                "still_psnr_pooled": _psnr(out["still_mse"].mean())})
+    return out
+
+
+def video_warp_error(frames, motion_from=None, block=16, radius=16):
+    """Warping error: what is left between consecutive frames of `frames` after frame t + 1 has been displaced block by block by motion vectors — the video's own
+    (motion_from None), or those of `motion_from`, the source video of an edit (same shape), whose motion the edit is expected to keep.  Returns float64 device
+    tensors per pair, shaped [F - 1] / [B, T - 1]: "warp_mse" = sum(sse) / (3 Hb Wb block^2 255^2) on the [0, 1] scale over the pixels that belong to a block,
+    "warp_psnr" = 10 log10(1 / (mse + 1e-8)) (video_metrics' formula), "still_mse" / "still_psnr" the same at zero displacement; pooled 0-dim "warp_mse_mean",
+    "warp_psnr_pooled" = the PSNR of the mean mse, "still_mse_mean", "still_psnr_pooled"; and "status" (int32 [1], always 0 here: searched vectors stay inside
+    the frame).  Nothing here waits for the device."""
+    M.check_frames(frames, "video_warp_error", motion_from)
+    M.check_block(block, radius, frames.shape[-3], frames.shape[-2], "video_warp_error")
+    mv = M.block_motion(frames if motion_from is None else motion_from, block, radius)["mv"]
+    w = M.warp_sse(frames, mv)
+    out = _warp_pooled(_warp_curves(w["sse"], w["sse0"], block))
+    out["status"] = w["status"]
+    return out
+
+
+class VideoMotion:
+    """Streaming video_motion and video_warp_error for long videos that arrive clip by clip.  `update(frames, motion_from=None)` continues the current video with a
+    clip, uint8 [F, H, W, 3] (F >= 1), and carries the clip's last frame (and the last frame of `motion_from`, the matching clip of an edit's source video) on the
+    device, so that the pair across the clip boundary is measured like any other; `new_video()` closes the current video; `finalize()` closes it too and returns
+    "videos" (an int), per curve of video_motion and video_warp_error a list with one float64 [n_v - 1] tensor per video, and "<curve>_mean" float64 [videos]
+    ("warp_psnr_pooled" / "still_psnr_pooled": the PSNR of a video's mean mse).  The motion statistics are those of `frames`; the warping error uses the vectors
+    of `motion_from` where a video is fed with one (every clip of a video, or none).  Every pair's figures come from its two frames alone: a video fed in pieces
+    gives the bits of the video fed whole.  Nothing waits for the device."""
+
+    def __init__(self, block=16, radius=16, top_fraction=0.05):
+        M.check_block(block, radius, block, block, "VideoMotion")
+        M.top_count(top_fraction, 1)
+        self.block, self.radius, self.top_fraction = block, radius, top_fraction
+        self._videos, self._open = [], None
+
+    def update(self, frames, motion_from=None):
+        if isinstance(frames, torch.Tensor) and frames.dim() != 4:
+            raise ValueError(f"VideoMotion.update: one video's clip [F, H, W, 3], got {tuple(frames.shape)}")
+        M.check_frames(frames, "VideoMotion.update", motion_from, pairs_within=False)
+        M.check_block(self.block, self.radius, frames.shape[1], frames.shape[2], "VideoMotion.update")
+        st = self._open
+        if st is None:
+            st = self._open = {"last": None, "src_last": None, "with_src": motion_from is not None, "frames": 0, "curves": {k: [] for k in MOTION_CURVES + WARP_CURVES}}
+        elif st["with_src"] != (motion_from is not None):
+            raise ValueError("VideoMotion.update: pass motion_from for every clip of a video or for none")
+        elif st["last"].shape[1:] != frames.shape[1:]:
+            raise ValueError(f"VideoMotion.update: the video's frames are {tuple(st['last'].shape[1:])}, this clip's {tuple(frames.shape[1:])}")
+        seq = frames if st["last"] is None else torch.cat([st["last"], frames])
+        src = motion_from if (motion_from is None or st["src_last"] is None) else torch.cat([st["src_last"], motion_from])
+        out = None
+        if seq.shape[0] >= 2:
+            out, r = _motion_curves(seq, self.block, self.radius, self.top_fraction)
+            mv = r["mv"] if src is None else M.block_motion(src, self.block, self.radius)["mv"]
+            w = M.warp_sse(seq, mv)
+            out.update(_warp_curves(w["sse"], w["sse0"], self.block))
+            for k, v in out.items():
+                st["curves"][k].append(v)
+        st["last"] = frames[-1:].clone()
+        st["src_last"] = None if motion_from is None else motion_from[-1:].clone()
+        st["frames"] += frames.shape[0]
+        return out
+
+    def new_video(self):
+        st = self._open
+        if st is None:
+            return
+        if st["frames"] < 2:
+            raise ValueError(f"VideoMotion: the current video has {st['frames']} frame(s); a video needs at least 2")
+        self._videos.append({k: torch.cat(v) for k, v in st["curves"].items()})
+        self._open = None
+
+    def finalize(self):
+        self.new_video()
+        if not self._videos:
+            raise RuntimeError("VideoMotion.finalize: no update yet")
+        out = {"videos": len(self._videos)}
+        for k in MOTION_CURVES + WARP_CURVES:
+            out[k] = [v[k] for v in self._videos]
+            if k.endswith("_psnr"):
+                continue
+            out[f"{k}_mean"] = torch.stack([v[k].mean() for v in self._videos])
+        out["warp_psnr_pooled"], out["still_psnr_pooled"] = _psnr(out["warp_mse_mean"]), _psnr(out["still_mse_mean"])
         return out
