@@ -65,6 +65,26 @@ def _randn(shape, seed, scale=1.0):
     return (scale * torch.randn(shape, generator=torch.Generator().manual_seed(seed))).to(BF)
 
 
+def _launch_counts(forward):
+    """{kernel name: launches} of one call of `forward`, after a warm-up call.  kernels.PROFILE keeps tg_gemm_bf16 under names that carry the shape
+    (`gemm_M.._N.._K.._epi..`): they are counted together as "gemm"."""
+    from tokensgen_amd import kernels as K
+    forward()
+    K.PROFILE.clear()
+    was = K.PROFILE_ON[0]
+    try:
+        K.PROFILE_ON[0] = True
+        forward()
+        counts = {}
+        for name, events in K.PROFILE.items():
+            name = "gemm" if name.startswith("gemm_M") else name
+            counts[name] = counts.get(name, 0) + len(events)
+    finally:
+        K.PROFILE_ON[0] = was
+        K.PROFILE.clear()
+    return counts
+
+
 # ---------------------------------------------------------------------------------------------------- tg_text_embed
 @pytest.mark.timeout(120)
 @pytest.mark.parametrize("B,S,D", [(3, 21, 128), (2, 77, 512), (1, 1, 64)])
@@ -214,6 +234,15 @@ def test_a_prompt_s_feature_does_not_depend_on_the_call(rule, gold, tiny, tiny_f
         assert torch.equal(m.encode_text(ids), tiny_features[rule])
     finally:
         m.prompts_per_launch = 64
+
+
+@pytest.mark.timeout(120)
+def test_launches_per_forward(gold, tiny):
+    """2 prompts through a tower of L layers: the embedding, ten launches per block, the final LayerNorm, the projection.  No other kernel."""
+    m, ids = tiny["argmax"], gold["ids"][:2]
+    L = m.config.num_hidden_layers
+    assert _launch_counts(lambda: m.encode_text(ids)) == {"text_embed": 1, "gemm": 4 * L + 1, "layernorm": 2 * L + 1, "t5_attention": L, "residual_add": 2 * L,
+                                                          "vit_act": L}
 
 
 @pytest.mark.timeout(120)

@@ -40,6 +40,26 @@ def _randn(shape, seed, scale=1.0):
     return (scale * torch.randn(shape, generator=torch.Generator().manual_seed(seed))).to(BF)
 
 
+def _launch_counts(forward):
+    """{kernel name: launches} of one call of `forward`, after a warm-up call.  kernels.PROFILE keeps tg_gemm_bf16 under names that carry the shape
+    (`gemm_M.._N.._K.._epi..`): they are counted together as "gemm"."""
+    from tokensgen_amd import kernels as K
+    forward()
+    K.PROFILE.clear()
+    was = K.PROFILE_ON[0]
+    try:
+        K.PROFILE_ON[0] = True
+        forward()
+        counts = {}
+        for name, events in K.PROFILE.items():
+            name = "gemm" if name.startswith("gemm_M") else name
+            counts[name] = counts.get(name, 0) + len(events)
+    finally:
+        K.PROFILE_ON[0] = was
+        K.PROFILE.clear()
+    return counts
+
+
 # ---------------------------------------------------------------------------------------------------- kernels
 @pytest.mark.timeout(120)
 @pytest.mark.parametrize("rows,D", [(1, 128), (453, 128), (1, 4096), (453, 4096)])
@@ -146,6 +166,15 @@ def test_tiny_model_vs_library_float64(case, gold, tiny, parity):
     p = c["positions"]
     library = R.rel_l2(c["bf16"], c["f64"])
     parity(R.rel_l2(out.cpu()[p[:, 0], p[:, 1]], c["f64"]), 1.5 * library, f"T5 tiny {case}: error against float64, bound 1.5 x the library's bf16 run ({library:.3e})")
+
+
+@pytest.mark.timeout(120)
+def test_launches_per_forward(gold, tiny):
+    """a [2, 7] id batch through an encoder of L layers: ten launches per block and the final norm.  No other kernel."""
+    ids = gold["cases"]["s7"]["input_ids"].to(DEV)
+    assert ids.shape == (2, 7)
+    L = tiny.config.num_layers
+    assert _launch_counts(lambda: tiny(ids)) == {"gemm": 4 * L, "rmsnorm": 2 * L + 1, "t5_attention": L, "residual_add": 2 * L, "gated_gelu": L}
 
 
 @pytest.mark.timeout(300)

@@ -51,6 +51,26 @@ def _randn(shape, seed, scale=1.0):
     return (scale * torch.randn(shape, generator=torch.Generator().manual_seed(seed))).to(BF)
 
 
+def _launch_counts(forward):
+    """{kernel name: launches} of one call of `forward`, after a warm-up call.  kernels.PROFILE keeps tg_gemm_bf16 under names that carry the shape
+    (`gemm_M.._N.._K.._epi..`): they are counted together as "gemm"."""
+    from tokensgen_amd import kernels as K
+    forward()
+    K.PROFILE.clear()
+    was = K.PROFILE_ON[0]
+    try:
+        K.PROFILE_ON[0] = True
+        forward()
+        counts = {}
+        for name, events in K.PROFILE.items():
+            name = "gemm" if name.startswith("gemm_M") else name
+            counts[name] = counts.get(name, 0) + len(events)
+    finally:
+        K.PROFILE_ON[0] = was
+        K.PROFILE.clear()
+    return counts
+
+
 # ---------------------------------------------------------------------------------------------------- kernels
 @pytest.mark.timeout(120)
 @pytest.mark.parametrize("H,W,p", [(40, 40, 8), (30, 30, 6), (16, 48, 8)])
@@ -222,6 +242,17 @@ def test_a_frame_s_feature_does_not_depend_on_the_call(kind, gold, tiny, tiny_fe
         assert torch.equal(m.encode_frames(frames), tiny_features[kind])
     finally:
         m.frames_per_launch = 64
+
+
+@pytest.mark.timeout(120)
+@pytest.mark.parametrize("kind", KINDS)
+def test_launches_per_forward(kind, gold, tiny):
+    """2 bf16 frames through a model of L layers: the patch rows, the patch GEMM, the assembly, ten launches per block, the class-token LayerNorm; CLIP adds
+    pre_layrnorm and the projection.  No other kernel."""
+    m, frames = tiny[kind], gold[kind]["frames"][:2].to(DEV)
+    L, clip = m.config.num_hidden_layers, int(kind == "clip")
+    assert _launch_counts(lambda: m.encode_frames(frames)) == {"vit_patch_rows": 1, "vit_assemble": 1, "gemm": 4 * L + 1 + clip, "layernorm": 2 * L + 1 + clip,
+                                                               "t5_attention": L, "residual_add": 2 * L, "vit_act": L}
 
 
 @pytest.mark.timeout(120)

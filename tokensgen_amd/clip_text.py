@@ -6,7 +6,7 @@ with CAUSAL self-attention and heads of 64, `final_layer_norm`, one pooled row p
 Per call (csrc/clip_text.hip, csrc/vit.hip, csrc/t5.hip; DESIGN.md §8g): x = tg_text_embed(ids, token table, position table);  per block  h = tg_layernorm(x);
 qkv = tg_gemm_bf16(h, q/8 | k | v);  a = tg_t5_attention(qkv, causal table);  x = tg_residual_add(x, tg_gemm_bf16(a, o));  h = tg_layernorm(x);
 x = tg_residual_add(x, tg_gemm_bf16(tg_vit_act(tg_gemm_bf16(h, fc1)), fc2));  then tg_layernorm, the pooled rows picked on the device, tg_gemm_bf16 for the projection.
-q_proj's weight and bias are multiplied by 1/8 = 64 ** -0.5 at load (exact in bf16), so tg_t5_attention, which has no scale, serves as it is.
+The blocks, the packed storage and the module plumbing are encoder.PreLNTower's; q | k | v carries q pre-scaled by 1/8 (encoder.py says why that is exact).
 
 The causal mask is tg_t5_attention's bias-by-distance table: 0 for key - query <= 0, -inf for key - query > 0 (`causal_table`).  Key 0 is visible to every query, so
 every row maximum is finite, a masked term is exp(-inf) = 0 exactly whatever its (finite) score, and a masked key adds an exact 0 to P V.  -inf and not a large finite
@@ -18,9 +18,8 @@ No padding mask is needed: attention is causal, so the pooled row sees itself an
 it, and with every later token replaced are equal to the bit (tests/test_clip_text_cpu.py).  `attention_mask` may be None or a right-padded mask that covers the pooled
 position; anything else (left padding, holes, a masked pooled position) is refused.
 
-A prompt's feature does not depend on its batch mates: every kernel works per row or per (sequence, head), and every GEMM is launched with at least 1024 rows, the
-count from which tg_gemm_bf16 changes kernels (`_gemm_rows`, as vit.ViTEncoder).  There is no CPU path: construction and loading work on any device, a forward needs
-the GPU.  No weights ship, and the tokenizer is the caller's (`encode_prompts` takes a transformers.CLIPTokenizer)."""
+A prompt's feature does not depend on its batch mates: every GEMM is launched with at least 1024 rows (encoder.gemm_rows).  There is no CPU path: construction and
+loading work on any device, a forward needs the GPU.  No weights ship, and the tokenizer is the caller's (`encode_prompts` takes a transformers.CLIPTokenizer)."""
 import json
 import os
 from collections import OrderedDict
@@ -29,10 +28,9 @@ from types import SimpleNamespace
 import torch
 
 from . import kernels as K
+from .encoder import PreLNTower, check_gemm_shapes, config_dict, read_checkpoint
 
-BF16 = torch.bfloat16
 MAX_POSITIONS = 512                # tg_t5_attention keeps one head's K and V in LDS
-GEMM_BIG_ROWS = 1024               # csrc/gemm_plan.h: from this many rows on (and N % 256 == 0) tg_gemm_bf16 launches a 256 x 256 kernel
 
 # text_config of openai/clip-vit-base-patch32
 _DEFAULTS = dict(vocab_size=49408, hidden_size=512, intermediate_size=2048, num_hidden_layers=12, num_attention_heads=8, max_position_embeddings=77,
@@ -74,77 +72,45 @@ def pooled_positions(input_ids, eos_token_id):
     return hit.int().argmax(dim=-1)
 
 
-class CLIPTextEncoder:
+class CLIPTextEncoder(PreLNTower):
+    _frozen = "requires_grad: the text tower has no backward pass here (it is a frozen feature extractor of a metric)"
+
     def __init__(self, config=None, device="cuda", **kw):
-        raw = {k: v for k, v in (vars(config) if hasattr(config, "__dict__") else dict(config or {})).items() if not k.startswith("_")}
-        raw.update(kw)
         cfg = dict(_DEFAULTS)
-        cfg.update({k: v for k, v in raw.items() if k in cfg and v is not None})
-        c = self.config = SimpleNamespace(**cfg)
-        if c.hidden_size % c.num_attention_heads or c.hidden_size // c.num_attention_heads != 64:
-            raise NotImplementedError(f"hidden_size / num_attention_heads = {c.hidden_size} / {c.num_attention_heads}: tg_t5_attention has head dimension 64 only")
-        if c.hidden_act not in K.VIT_ACT:
-            raise NotImplementedError(f"hidden_act = {c.hidden_act!r}: tg_vit_act has 'gelu' (exact) and 'quick_gelu' only")
-        D, I = c.hidden_size, c.intermediate_size
+        cfg.update({k: v for k, v in config_dict(config, **kw).items() if k in cfg and v is not None})
+        c = SimpleNamespace(**cfg)
+        super().__init__(c, device)
+        D = c.hidden_size
         self.out_dim = c.projection_dim
-        for what, n, k in (("q | k | v", 3 * D, D), ("o", D, D), ("fc1", I, D), ("fc2", D, I), ("text_projection", self.out_dim, D)):
-            if n % 128 or k % 64:
-                raise NotImplementedError(f"the {what} projection [{n}, {k}] breaks tg_gemm_bf16's N % 128 == 0 / K % 64 == 0 rule")
+        check_gemm_shapes(self._block_gemms() + [("text_projection", self.out_dim, D)])
         if not 1 <= c.max_position_embeddings <= MAX_POSITIONS:
             raise NotImplementedError(f"max_position_embeddings = {c.max_position_embeddings}: tg_t5_attention keeps a head's keys in LDS, S <= {MAX_POSITIONS}")
-        self.dtype = BF16
-        self.device = torch.device(device)
         self.prompts_per_launch = 64
-        z = lambda *s: torch.zeros(*s, dtype=BF16, device=self.device)
-        one = lambda *s: torch.ones(*s, dtype=BF16, device=self.device)
-        # the packed weights are the storage (packed once, at load): q | k | v fused with q pre-scaled by 1/8
-        w = self._w = {"tok": z(c.vocab_size, D), "pos": z(c.max_position_embeddings, D), "ln_w": one(D), "ln_b": z(D), "proj": z(self.out_dim, D)}
-        for i in range(c.num_hidden_layers):
-            w.update({f"l{i}.ln1_w": one(D), f"l{i}.ln1_b": z(D), f"l{i}.qkv_w": z(3 * D, D), f"l{i}.qkv_b": z(3 * D), f"l{i}.o_w": z(D, D), f"l{i}.o_b": z(D),
-                      f"l{i}.ln2_w": one(D), f"l{i}.ln2_b": z(D), f"l{i}.fc1_w": z(I, D), f"l{i}.fc1_b": z(I), f"l{i}.fc2_w": z(D, I), f"l{i}.fc2_b": z(D)})
-        self._tables, self._ws, self._status = {}, {}, None
+        z, one = self._zeros, self._ones
+        # the packed weights are the storage (packed once, at load)
+        self._w = {"tok": z(c.vocab_size, D), "pos": z(c.max_position_embeddings, D), "ln_w": one(D), "ln_b": z(D), "proj": z(self.out_dim, D)}
+        self._alloc_layers()
+
+    def _drop_caches(self):
+        super()._drop_caches()
+        self._tables, self._status = {}, None
 
     # ---------------------------------------------------------------------------------------------- weights
     def _views(self):
-        """library name -> (view of the packed storage, scale applied at load).  Row order of the fused weight: q rows, then k, then v."""
-        c, w, D = self.config, self._w, self.config.hidden_size
+        """library name -> (view of the packed storage, scale applied at load)"""
+        c, w = self.config, self._w
         v = OrderedDict()
         v["text_model.embeddings.token_embedding.weight"] = (w["tok"], 1.0)
         v["text_model.embeddings.position_embedding.weight"] = (w["pos"], 1.0)
         for i in range(c.num_hidden_layers):
             e = f"text_model.encoder.layers.{i}."
-            for j, n in enumerate("qkv"):
-                s = 0.125 if n == "q" else 1.0
-                v[e + f"self_attn.{n}_proj.weight"] = (w[f"l{i}.qkv_w"][j * D:(j + 1) * D], s)
-                v[e + f"self_attn.{n}_proj.bias"] = (w[f"l{i}.qkv_b"][j * D:(j + 1) * D], s)
-            v[e + "self_attn.out_proj.weight"], v[e + "self_attn.out_proj.bias"] = (w[f"l{i}.o_w"], 1.0), (w[f"l{i}.o_b"], 1.0)
-            v[e + "layer_norm1.weight"], v[e + "layer_norm1.bias"] = (w[f"l{i}.ln1_w"], 1.0), (w[f"l{i}.ln1_b"], 1.0)
-            v[e + "layer_norm2.weight"], v[e + "layer_norm2.bias"] = (w[f"l{i}.ln2_w"], 1.0), (w[f"l{i}.ln2_b"], 1.0)
-            for n in ("fc1", "fc2"):
-                v[e + f"mlp.{n}.weight"], v[e + f"mlp.{n}.bias"] = (w[f"l{i}.{n}_w"], 1.0), (w[f"l{i}.{n}_b"], 1.0)
+            self._layer_views(v, i, e + "self_attn.", "out_proj", e + "layer_norm1.", e + "layer_norm2.", e + "mlp.")
         v["text_model.final_layer_norm.weight"], v["text_model.final_layer_norm.bias"] = (w["ln_w"], 1.0), (w["ln_b"], 1.0)
         v["text_projection.weight"] = (w["proj"], 1.0)
         return v
 
-    def state_dict(self):
-        """The library's names -> bf16 tensors as they were loaded (q_proj handed out without its 1/8: a copy; everything else a view of the storage)."""
-        return OrderedDict((k, t if s == 1.0 else t * (1.0 / s)) for k, (t, s) in self._views().items())
-
-    def load_state_dict(self, state_dict, strict=True):
-        views = self._views()
-        sd = canonical_state_dict(state_dict)
-        unexpected = [k for k in sd if k not in views]
-        missing = [k for k in views if k not in sd]
-        bad = [f"{k}: {tuple(sd[k].shape)} != {tuple(views[k][0].shape)}" for k in sd if k in views and sd[k].shape != views[k][0].shape]
-        if bad or (strict and (missing or unexpected)):
-            raise RuntimeError(f"CLIPTextEncoder.load_state_dict: size mismatch {bad}; missing keys {missing}; unexpected keys {unexpected}")
-        with torch.no_grad():
-            for k, t in sd.items():
-                if k in views:
-                    dst, s = views[k]
-                    t = t.to(device=self.device, dtype=BF16)
-                    dst.copy_(t if s == 1.0 else t * s)              # * 1/8 in bf16: exact (a power of two)
-        return SimpleNamespace(missing_keys=missing, unexpected_keys=unexpected)
+    def _canonical(self, state_dict):
+        return canonical_state_dict(state_dict)
 
     @classmethod
     def from_pretrained(cls, path, device="cuda", **kw):
@@ -156,75 +122,22 @@ class CLIPTextEncoder:
             cfg = dict(cfg["text_config"], projection_dim=cfg.get("projection_dim", cfg["text_config"].get("projection_dim", 512)))
         cfg.update(kw)
         m = cls(cfg, device=device)
-        st = os.path.join(path, "model.safetensors")
-        if os.path.exists(st):
-            from safetensors.torch import load_file
-            sd = load_file(st)
-        else:
-            sd = torch.load(os.path.join(path, "pytorch_model.bin"), map_location="cpu", weights_only=True)
-        m.load_state_dict(sd, strict=True)
+        m.load_state_dict(read_checkpoint(path), strict=True)
         return m
 
-    def to(self, device=None, *unused, **kw):
-        device = kw.get("device", device)
-        if device is not None and not isinstance(device, torch.dtype) and torch.device(device) != self.device:
-            self.device = torch.device(device)
-            self._w = {k: t.to(self.device) for k, t in self._w.items()}
-            self._tables, self._ws, self._status = {}, {}, None
-        return self
-
-    def eval(self):
-        return self
-
-    def requires_grad_(self, flag=False):
-        if flag:
-            raise NotImplementedError("requires_grad: the text tower has no backward pass here (it is a frozen feature extractor of a metric)")
-        return self
-
     # ---------------------------------------------------------------------------------------------- forward
-    @staticmethod
-    def _gemm_rows(rows):
-        """Rows a GEMM over `rows` real rows is launched with: at least the 1024 from which tg_gemm_bf16 changes kernels (vit.ViTEncoder._gemm_rows), so a prompt's
-        feature does not depend on its batch mates.  The extra rows are workspace, computed and ignored: a GEMM row depends on its own input row alone."""
-        return max(rows, GEMM_BIG_ROWS)
-
-    def _workspace(self, B, S):
-        ws = self._ws.get((B, S))
-        if ws is None:
-            c, D = self.config, self.config.hidden_size
-            rt, rb = self._gemm_rows(B * S), self._gemm_rows(B)
-            e = lambda r, k: torch.zeros(r, k, dtype=BF16, device=self.device)      # zeros: the ignored rows stay finite
-            ws = SimpleNamespace(x=e(rt, D), h=e(rt, D), qkv=e(rt, 3 * D), a=e(rt, D), o=e(rt, D), f=e(rt, c.intermediate_size), pool=e(rb, D), proj=e(rb, self.out_dim))
-            if len(self._ws) >= 2:
-                self._ws = {}
-            self._ws[(B, S)] = ws
-        return ws
-
     def _trunk(self, ids, rows, out):
         """ids int32 [B, S] and rows int64 [B] (b * S + pooled position), both on the device -> out fp32 [B, out_dim]"""
         c, w, D, (B, S) = self.config, self._w, self.config.hidden_size, ids.shape
-        ws = self._workspace(B, S)
+        ws = self._workspace((B, S), B * S, {"pool": (B, D), "proj": (B, self.out_dim)})
         if S not in self._tables:
             self._tables[S] = causal_table(c.num_attention_heads, S, self.device)
         if self._status is None:                                          # tg_text_embed's count of refused ids: encode_text validated them on the host, so it stays 0 and is never read back
             self._status = torch.zeros(1, dtype=torch.int32, device=self.device)
         K.text_embed(ids.view(-1), S, w["tok"], w["pos"], ws.x, self._status)
         ws.x[B * S:].zero_()                                              # the ignored rows restart from zero: they would add up over the calls otherwise
-        qkv, att = ws.qkv[:B * S].view(B, S, 3 * D), ws.a[:B * S].view(B, S, D)
-        eps = c.layer_norm_eps
-        for i in range(c.num_hidden_layers):
-            p = f"l{i}."
-            K.layernorm(ws.x, w[p + "ln1_w"], w[p + "ln1_b"], ws.h, eps)
-            K.gemm(ws.h, w[p + "qkv_w"], w[p + "qkv_b"], ws.qkv)
-            K.t5_attention(qkv, self._tables[S], att, c.num_attention_heads)
-            K.gemm(ws.a, w[p + "o_w"], w[p + "o_b"], ws.o)
-            K.residual_add(ws.x, ws.o, ws.x)
-            K.layernorm(ws.x, w[p + "ln2_w"], w[p + "ln2_b"], ws.h, eps)
-            K.gemm(ws.h, w[p + "fc1_w"], w[p + "fc1_b"], ws.f)
-            K.vit_act(ws.f, ws.f, c.hidden_act)
-            K.gemm(ws.f, w[p + "fc2_w"], w[p + "fc2_b"], ws.o)
-            K.residual_add(ws.x, ws.o, ws.x)
-        K.layernorm(ws.x, w["ln_w"], w["ln_b"], ws.h, eps)
+        self._run_blocks(ws, B, S, self._tables[S])
+        K.layernorm(ws.x, w["ln_w"], w["ln_b"], ws.h, c.layer_norm_eps)
         torch.index_select(ws.h, 0, rows, out=ws.pool[:B])                # the pooled rows, picked on the device: a copy of B rows, no host synchronisation
         K.gemm(ws.pool, w["proj"], None, ws.proj)
         out.copy_(ws.proj[:B])

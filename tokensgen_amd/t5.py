@@ -9,6 +9,7 @@ Per block (csrc/t5.hip):  h = tg_rmsnorm(x);  qkv = tg_gemm_bf16
 tg_gemm_bf16(a, o));  h = tg_rmsnorm(x);  g = tg_gated_gelu(tg_gemm_bf16(h, wi_0|wi_1));  x = tg_residual_add(x, tg_gemm_bf16(g, wo));  then the final norm.
 The embedding lookup is a torch gather on the device (plumbing).  The relative-position bias is built on the HOST once per sequence length, as an fp32 table
 [heads, 2 S - 1] indexed by j - i + S - 1: the library's float32 `log` decides the bucket boundaries, and the same torch ops on the host give the same buckets.
+The module plumbing is encoder.FrozenEncoder's; the block is T5's own (RMSNorm, no biases, gated GELU, no softmax scale, an unpadded workspace).
 There is no CPU path: construction, loading and weight packing work on any device, a forward needs the GPU.  The tokenizer is the caller's (transformers.T5Tokenizer
 or any object with its call interface)."""
 import json
@@ -21,8 +22,7 @@ from types import SimpleNamespace
 import torch
 
 from . import kernels as K
-
-BF16 = torch.bfloat16
+from .encoder import BF16, FrozenEncoder, check_gemm_shapes, config_dict
 logger = logging.getLogger(__name__)
 MAX_SEQUENCE_LENGTH = 512          # tg_t5_attention keeps one head's K and V in LDS
 
@@ -64,36 +64,36 @@ class T5EncoderOutput(tuple):
         return self[0]
 
 
-class T5EncoderModel:
+class T5EncoderModel(FrozenEncoder):
+    _tied = frozenset(("shared.weight", "encoder.embed_tokens.weight"))
+    _frozen = "the T5 encoder has no backward pass here: it is frozen in every reference run"
+
     def __init__(self, config=None, device="cuda", **kw):
         cfg = dict(_DEFAULTS)
-        cfg.update({k: v for k, v in (vars(config) if hasattr(config, "__dict__") else dict(config or {})).items() if not k.startswith("_")})
-        cfg.update(kw)
+        cfg.update(config_dict(config, **kw))
         c = self.config = SimpleNamespace(**cfg)
         if c.d_kv != 64:
             raise NotImplementedError(f"d_kv = {c.d_kv}: tg_t5_attention has head dimension 64 only")
         if c.feed_forward_proj != "gated-gelu":
             raise NotImplementedError(f"feed_forward_proj = {c.feed_forward_proj!r}: only the gated-gelu feed-forward (gelu_new * linear) of T5 v1.1 is built")
         inner = c.num_heads * 64
-        for what, n, k in (("q | k | v", 3 * inner, c.d_model), ("o", c.d_model, inner), ("wi_0 | wi_1", 2 * c.d_ff, c.d_model), ("wo", c.d_model, c.d_ff)):
-            if n % 128 or k % 64:
-                raise NotImplementedError(f"the {what} projection [{n}, {k}] breaks tg_gemm_bf16's N % 128 == 0 / K % 64 == 0 rule")
+        check_gemm_shapes((("q | k | v", 3 * inner, c.d_model), ("o", c.d_model, inner), ("wi_0 | wi_1", 2 * c.d_ff, c.d_model), ("wo", c.d_model, c.d_ff)))
         self.inner_dim = inner
-        self.dtype = BF16
-        self.device = torch.device(device)
-        z = lambda *s: torch.zeros(*s, dtype=BF16, device=self.device)
-        one = lambda *s: torch.ones(*s, dtype=BF16, device=self.device)
+        super().__init__(device)
+        z, one = self._zeros, self._ones
         # the packed weights ARE the storage: state_dict() hands out views under the library's names, load_state_dict() copies into them (packed once, at load)
         self._w = {"emb": z(c.vocab_size, c.d_model), "rel_bias": z(c.relative_attention_num_buckets, c.num_heads), "final_ln": one(c.d_model)}
         for i in range(c.num_layers):
             self._w.update({f"l{i}.qkv": z(3 * inner, c.d_model), f"l{i}.o": z(c.d_model, inner), f"l{i}.wi": z(2 * c.d_ff, c.d_model), f"l{i}.wo": z(c.d_model, c.d_ff),
                             f"l{i}.ln0": one(c.d_model), f"l{i}.ln1": one(c.d_model)})
+
+    def _drop_caches(self):
         self._bias = {}            # S -> fp32 [heads, 2 S - 1] on the device
         self._ws = {}              # (B, S) -> buffers; one shape resident
 
     # ---------------------------------------------------------------------------------------------- weights
     def _views(self):
-        """library name -> view of the packed storage.  Row order of the fused weights: q rows, then k, then v; wi_0 rows, then wi_1."""
+        """library name -> (view of the packed storage, 1.0: nothing is scaled at load).  Row order of the fused weights: q rows, then k, then v; wi_0 rows, then wi_1."""
         c, w, inner = self.config, self._w, self.inner_dim
         v = OrderedDict()
         v["shared.weight"] = w["emb"]
@@ -111,25 +111,12 @@ class T5EncoderModel:
             v[f + "DenseReluDense.wo.weight"] = w[f"l{i}.wo"]
             v[f + "layer_norm.weight"] = w[f"l{i}.ln1"]
         v["encoder.final_layer_norm.weight"] = w["final_ln"]
-        return v
-
-    def state_dict(self):
-        return self._views()
+        return OrderedDict((k, (t, 1.0)) for k, t in v.items())
 
     def load_state_dict(self, state_dict, strict=True):
-        views = self._views()
-        tied = {"shared.weight", "encoder.embed_tokens.weight"}
-        unexpected = [k for k in state_dict if k not in views]
-        missing = [k for k in views if k not in state_dict and not (k in tied and tied & set(state_dict))]
-        bad = [f"{k}: {tuple(state_dict[k].shape)} != {tuple(views[k].shape)}" for k in state_dict if k in views and state_dict[k].shape != views[k].shape]
-        if bad or (strict and (missing or unexpected)):
-            raise RuntimeError(f"T5EncoderModel.load_state_dict: size mismatch {bad}; missing keys {missing}; unexpected keys {unexpected}")
-        with torch.no_grad():
-            for k, t in state_dict.items():
-                if k in views:
-                    views[k].copy_(t.to(BF16))
-        self._bias = {}
-        return SimpleNamespace(missing_keys=missing, unexpected_keys=unexpected)
+        res = super().load_state_dict(state_dict, strict)
+        self._bias = {}            # built from relative_attention_bias.weight
+        return res
 
     @classmethod
     def from_pretrained(cls, path, subfolder="text_encoder", device="cuda", **unused):
@@ -150,29 +137,12 @@ class T5EncoderModel:
             sd = load_file(os.path.join(d, fn))
             m.load_state_dict(sd, strict=False)
             seen |= set(sd)
-        views = m._views()
-        tied = {"shared.weight", "encoder.embed_tokens.weight"}
+        views, tied = m._views(), cls._tied
         missing = [k for k in views if k not in seen and not (k in tied and tied & seen)]
         unexpected = [k for k in seen if k not in views]
         if missing or unexpected:
             raise RuntimeError(f"T5EncoderModel.from_pretrained({d}): missing keys {missing}; unexpected keys {unexpected}")
         return m
-
-    def to(self, device=None, *unused, **kw):
-        device = kw.get("device", device)
-        if device is not None and not isinstance(device, torch.dtype) and torch.device(device) != self.device:
-            self.device = torch.device(device)
-            self._w = {k: t.to(self.device) for k, t in self._w.items()}
-            self._bias, self._ws = {}, {}
-        return self
-
-    def eval(self):
-        return self
-
-    def requires_grad_(self, flag=False):
-        if flag:
-            raise NotImplementedError("the T5 encoder has no backward pass here: it is frozen in every reference run")
-        return self
 
     # ---------------------------------------------------------------------------------------------- forward
     def _bias_table(self, S):

@@ -7,12 +7,11 @@ Host mirror of two transformers models, both pre-LayerNorm ViTs with heads of 64
 Per call (csrc/vit.hip): rows = tg_vit_patch_rows(frames) with the preprocessing folded in;  tok = tg_vit_assemble(tg_gemm_bf16(rows, conv weight), cls,
 pos);  per block  h = tg_layernorm(x);  qkv = tg_gemm_bf16(h, q/8 | k | v);  a = tg_t5_attention(qkv, zero table);  x = tg_residual_add(x, tg_gemm_bf16(a, o));
 h = tg_layernorm(x);  x = tg_residual_add(x, tg_gemm_bf16(tg_vit_act(tg_gemm_bf16(h, fc1)), fc2));  then the final LayerNorm on the class-token rows only.
-q_proj's weight and bias are multiplied by 1/8 = 64 ** -0.5 at load (exact in bf16: a power of two), so tg_t5_attention, which has no scale, serves as it is.
+The blocks, the packed storage and the module plumbing are encoder.PreLNTower's; q | k | v carries q pre-scaled by 1/8 (encoder.py says why that is exact).
 
 uint8 frames go through video_io.prepare_video(..., (image_size, image_size), crop_to_fit=True): bicubic antialiased cover, then centre crop — CLIP's own
 preprocessing; for the DINO encoder a stated deviation from benchmark scripts that resize without cropping.
-A frame's feature does not depend on how many frames a call carries: every kernel works per row, per frame or per (frame, head), and every GEMM is launched with
-at least 1024 rows, the count from which tg_gemm_bf16 changes kernels (`_gemm_rows`), so a short batch takes the kernels a long one takes.
+A frame's feature does not depend on how many frames a call carries: every GEMM is launched with at least 1024 rows (encoder.gemm_rows).
 There is no CPU path: construction and loading work on any device, a forward needs the GPU.  No weights ship."""
 import json
 import os
@@ -23,10 +22,9 @@ from types import SimpleNamespace
 import torch
 
 from . import kernels as K
+from .encoder import BF16, PreLNTower, check_gemm_shapes, config_dict, read_checkpoint
 
-BF16 = torch.bfloat16
 MAX_TOKENS = 512                   # tg_t5_attention keeps one head's K and V in LDS
-GEMM_BIG_ROWS = 1024               # csrc/gemm_plan.h: from this many rows on (and N % 256 == 0) tg_gemm_bf16 launches a 256 x 256 kernel
 
 _DEFAULTS = {
     "vit": dict(hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072, hidden_act="gelu", layer_norm_eps=1e-12, image_size=224,
@@ -81,10 +79,11 @@ def canonical_state_dict(state_dict, kind):
     return out
 
 
-class ViTEncoder:
+class ViTEncoder(PreLNTower):
+    _frozen = "requires_grad: the image encoders have no backward pass here (they are frozen feature extractors of a metric)"
+
     def __init__(self, config=None, device="cuda", kind=None, **kw):
-        raw = {k: v for k, v in (vars(config) if hasattr(config, "__dict__") else dict(config or {})).items() if not k.startswith("_")}
-        raw.update(kw)
+        raw = config_dict(config, **kw)
         kind = kind or raw.pop("kind", None) or {"vit": "vit", "clip": "clip", "clip_vision_model": "clip"}.get(raw.get("model_type"), None)
         raw.pop("kind", None)
         if kind not in _DEFAULTS:
@@ -94,49 +93,40 @@ class ViTEncoder:
                                       f"CLIP vision tower only (got {({k: raw[k] for k in ('model_type',) + _DINOV2 if raw.get(k)})})")
         cfg = dict(_DEFAULTS[kind])
         cfg.update({k: v for k, v in raw.items() if k in cfg})
-        c = self.config = SimpleNamespace(kind=kind, **cfg)
+        c = SimpleNamespace(kind=kind, **cfg)
         self.kind = kind
-        if c.hidden_size % c.num_attention_heads or c.hidden_size // c.num_attention_heads != 64:
-            raise NotImplementedError(f"hidden_size / num_attention_heads = {c.hidden_size} / {c.num_attention_heads}: tg_t5_attention has head dimension 64 only")
-        if c.hidden_act not in K.VIT_ACT:
-            raise NotImplementedError(f"hidden_act = {c.hidden_act!r}: tg_vit_act has 'gelu' (exact) and 'quick_gelu' only")
+        super().__init__(c, device)
         if c.num_channels != 3 or (kind == "vit" and not c.qkv_bias):
             raise NotImplementedError("three input channels and q / k / v projections with bias only")
         if c.image_size % c.patch_size:
             raise NotImplementedError(f"image_size {c.image_size} is not a multiple of patch_size {c.patch_size}")
-        D, I, p = c.hidden_size, c.intermediate_size, c.patch_size
+        D, p = c.hidden_size, c.patch_size
         self.grid = c.image_size // p
         self.tokens = self.grid * self.grid + 1
         self.patch_k = 3 * p * p
         self.patch_kp = (self.patch_k + 63) // 64 * 64
         self.out_dim = c.projection_dim if kind == "clip" else D
-        gemms = [("patch", D, self.patch_kp), ("q | k | v", 3 * D, D), ("o", D, D), ("fc1", I, D), ("fc2", D, I)] + ([("visual_projection", self.out_dim, D)] if kind == "clip" else [])
-        for what, n, k in gemms:
-            if n % 128 or k % 64:
-                raise NotImplementedError(f"the {what} projection [{n}, {k}] breaks tg_gemm_bf16's N % 128 == 0 / K % 64 == 0 rule")
+        check_gemm_shapes([("patch", D, self.patch_kp)] + self._block_gemms() + ([("visual_projection", self.out_dim, D)] if kind == "clip" else []))
         if self.tokens > MAX_TOKENS:
             raise NotImplementedError(f"S = {self.tokens} tokens per image: tg_t5_attention keeps a head's keys in LDS, S <= {MAX_TOKENS}")
-        self.dtype = BF16
-        self.device = torch.device(device)
         self.frames_per_launch = 64
         self.image_mean, self.image_std = tuple(float(v) for v in c.image_mean), tuple(float(v) for v in c.image_std)
-        z = lambda *s: torch.zeros(*s, dtype=BF16, device=self.device)
-        one = lambda *s: torch.ones(*s, dtype=BF16, device=self.device)
-        # the packed weights are the storage (packed once, at load): the patch convolution as [D, Kp] rows with zero pad columns, q | k | v fused with q pre-scaled by 1/8
+        z, one = self._zeros, self._ones
+        # the packed weights are the storage (packed once, at load): the patch convolution as [D, Kp] rows with zero pad columns
         w = self._w = {"patch_w": z(D, self.patch_kp), "cls": z(D), "pos": z(self.tokens, D), "ln_w": one(D), "ln_b": z(D)}
         if kind == "vit":
             w["patch_b"] = z(D)
         else:
             w.update({"pre_w": one(D), "pre_b": z(D), "proj": z(self.out_dim, D)})
-        for i in range(c.num_hidden_layers):
-            w.update({f"l{i}.ln1_w": one(D), f"l{i}.ln1_b": z(D), f"l{i}.qkv_w": z(3 * D, D), f"l{i}.qkv_b": z(3 * D), f"l{i}.o_w": z(D, D), f"l{i}.o_b": z(D),
-                      f"l{i}.ln2_w": one(D), f"l{i}.ln2_b": z(D), f"l{i}.fc1_w": z(I, D), f"l{i}.fc1_b": z(I), f"l{i}.fc2_w": z(D, I), f"l{i}.fc2_b": z(D)})
+        self._alloc_layers()
+
+    def _drop_caches(self):
+        super()._drop_caches()
         self._zero_bias = None
-        self._ws = {}
 
     # ---------------------------------------------------------------------------------------------- weights
     def _views(self):
-        """canonical name -> (view of the packed storage, scale applied at load).  Row order of the fused weight: q rows, then k, then v."""
+        """canonical name -> (view of the packed storage, scale applied at load)"""
         c, w, D, p = self.config, self._w, self.config.hidden_size, self.config.patch_size
         v = OrderedDict()
         conv = w["patch_w"][:, :self.patch_k].view(D, 3, p, p)
@@ -154,16 +144,7 @@ class ViTEncoder:
             layer = lambda i: (f"vision_model.encoder.layers.{i}.self_attn.", "out_proj", f"vision_model.encoder.layers.{i}.layer_norm1.",
                                f"vision_model.encoder.layers.{i}.layer_norm2.", f"vision_model.encoder.layers.{i}.mlp.")
         for i in range(c.num_hidden_layers):
-            attn, o, ln1, ln2, mlp = layer(i)
-            for j, n in enumerate("qkv"):
-                s = 0.125 if n == "q" else 1.0
-                v[attn + f"{n}_proj.weight"] = (w[f"l{i}.qkv_w"][j * D:(j + 1) * D], s)
-                v[attn + f"{n}_proj.bias"] = (w[f"l{i}.qkv_b"][j * D:(j + 1) * D], s)
-            v[attn + o + ".weight"], v[attn + o + ".bias"] = (w[f"l{i}.o_w"], 1.0), (w[f"l{i}.o_b"], 1.0)
-            v[ln1 + "weight"], v[ln1 + "bias"] = (w[f"l{i}.ln1_w"], 1.0), (w[f"l{i}.ln1_b"], 1.0)
-            v[ln2 + "weight"], v[ln2 + "bias"] = (w[f"l{i}.ln2_w"], 1.0), (w[f"l{i}.ln2_b"], 1.0)
-            for n in ("fc1", "fc2"):
-                v[mlp + n + ".weight"], v[mlp + n + ".bias"] = (w[f"l{i}.{n}_w"], 1.0), (w[f"l{i}.{n}_b"], 1.0)
+            self._layer_views(v, i, *layer(i))
         if self.kind == "vit":
             v["layernorm.weight"], v["layernorm.bias"] = (w["ln_w"], 1.0), (w["ln_b"], 1.0)
         else:
@@ -171,25 +152,8 @@ class ViTEncoder:
             v["visual_projection.weight"] = (w["proj"], 1.0)
         return v
 
-    def state_dict(self):
-        """The library's in-memory names -> bf16 tensors as they were loaded (q_proj handed out without its 1/8: a copy; everything else a view of the storage)."""
-        return OrderedDict((k, t if s == 1.0 else t * (1.0 / s)) for k, (t, s) in self._views().items())
-
-    def load_state_dict(self, state_dict, strict=True):
-        views = self._views()
-        sd = canonical_state_dict(state_dict, self.kind)
-        unexpected = [k for k in sd if k not in views]
-        missing = [k for k in views if k not in sd]
-        bad = [f"{k}: {tuple(sd[k].shape)} != {tuple(views[k][0].shape)}" for k in sd if k in views and sd[k].shape != views[k][0].shape]
-        if bad or (strict and (missing or unexpected)):
-            raise RuntimeError(f"ViTEncoder.load_state_dict: size mismatch {bad}; missing keys {missing}; unexpected keys {unexpected}")
-        with torch.no_grad():
-            for k, t in sd.items():
-                if k in views:
-                    dst, s = views[k]
-                    t = t.to(device=self.device, dtype=BF16)
-                    dst.copy_(t if s == 1.0 else t * s)              # * 1/8 in bf16: exact (a power of two)
-        return SimpleNamespace(missing_keys=missing, unexpected_keys=unexpected)
+    def _canonical(self, state_dict):
+        return canonical_state_dict(state_dict, self.kind)
 
     @classmethod
     def from_pretrained(cls, path, device="cuda", kind=None, **kw):
@@ -205,56 +169,15 @@ class ViTEncoder:
                 cfg.update({k: v for k, v in json.load(f).items() if k in ("image_mean", "image_std")})
         cfg.update(kw)
         m = cls(cfg, device=device, kind=kind)
-        st = os.path.join(path, "model.safetensors")
-        if os.path.exists(st):
-            from safetensors.torch import load_file
-            sd = load_file(st)
-        else:
-            sd = torch.load(os.path.join(path, "pytorch_model.bin"), map_location="cpu", weights_only=True)
-        m.load_state_dict(sd, strict=True)
+        m.load_state_dict(read_checkpoint(path), strict=True)
         return m
 
-    def to(self, device=None, *unused, **kw):
-        device = kw.get("device", device)
-        if device is not None and not isinstance(device, torch.dtype) and torch.device(device) != self.device:
-            self.device = torch.device(device)
-            self._w = {k: t.to(self.device) for k, t in self._w.items()}
-            self._zero_bias, self._ws = None, {}
-        return self
-
-    def eval(self):
-        return self
-
-    def requires_grad_(self, flag=False):
-        if flag:
-            raise NotImplementedError("requires_grad: the image encoders have no backward pass here (they are frozen feature extractors of a metric)")
-        return self
-
     # ---------------------------------------------------------------------------------------------- forward
-    @staticmethod
-    def _gemm_rows(rows):
-        """Rows a GEMM over `rows` real rows is launched with.  tg_gemm_bf16 changes kernels at 1024 rows, and two kernels need not give the same bits; so every
-        GEMM here has at least 1024 rows (the extra rows of a short batch are workspace: zeros or stale values, computed and ignored — a GEMM row depends on its own
-        input row alone), and a frame's feature does not depend on the batch it travels in."""
-        return max(rows, GEMM_BIG_ROWS)
-
-    def _workspace(self, n):
-        ws = self._ws.get((n, self.frames_per_launch))
-        if ws is None:
-            c, D, S = self.config, self.config.hidden_size, self.tokens
-            rt, rp = self._gemm_rows(n * S), self._gemm_rows(n * (S - 1))
-            e = lambda r, k: torch.zeros(r, k, dtype=BF16, device=self.device)      # zeros: the ignored rows stay finite
-            ws = SimpleNamespace(rows=e(rp, self.patch_kp), patch=e(rp, D), x=e(rt, D), h=e(rt, D), qkv=e(rt, 3 * D), a=e(rt, D), o=e(rt, D), f=e(rt, c.intermediate_size),
-                                 cls=e(self._gemm_rows(n), D), proj=e(self._gemm_rows(n), self.out_dim))
-            if len(self._ws) >= 2:
-                self._ws = {}
-            self._ws[(n, self.frames_per_launch)] = ws
-        return ws
-
     def _trunk(self, frames, out):
         """frames bf16 [n, 3, s, s] in [-1, 1], n <= frames_per_launch -> out fp32 [n, out_dim]"""
         c, w, D, S, n = self.config, self._w, self.config.hidden_size, self.tokens, frames.shape[0]
-        ws = self._workspace(n)
+        ws = self._workspace((n, self.frames_per_launch), n * S,
+                             {"rows": (n * (S - 1), self.patch_kp), "patch": (n * (S - 1), D), "cls": (n, D), "proj": (n, self.out_dim)})
         if self._zero_bias is None:
             self._zero_bias = torch.zeros(c.num_attention_heads, 2 * S - 1, dtype=torch.float32, device=self.device)
         a, b = fold_preprocessing(self.image_mean, self.image_std)
@@ -268,19 +191,7 @@ class ViTEncoder:
         else:
             K.vit_assemble(ws.patch, w["cls"], w["pos"], tok)
             ws.x[n * S:].zero_()                                          # the ignored rows restart from zero: they would add up over the calls otherwise
-        qkv, att = ws.qkv[:n * S].view(n, S, 3 * D), ws.a[:n * S].view(n, S, D)
-        for i in range(c.num_hidden_layers):
-            p = f"l{i}."
-            K.layernorm(ws.x, w[p + "ln1_w"], w[p + "ln1_b"], ws.h, eps)
-            K.gemm(ws.h, w[p + "qkv_w"], w[p + "qkv_b"], ws.qkv)
-            K.t5_attention(qkv, self._zero_bias, att, c.num_attention_heads)
-            K.gemm(ws.a, w[p + "o_w"], w[p + "o_b"], ws.o)
-            K.residual_add(ws.x, ws.o, ws.x)
-            K.layernorm(ws.x, w[p + "ln2_w"], w[p + "ln2_b"], ws.h, eps)
-            K.gemm(ws.h, w[p + "fc1_w"], w[p + "fc1_b"], ws.f)
-            K.vit_act(ws.f, ws.f, c.hidden_act)
-            K.gemm(ws.f, w[p + "fc2_w"], w[p + "fc2_b"], ws.o)
-            K.residual_add(ws.x, ws.o, ws.x)
+        self._run_blocks(ws, n, S, self._zero_bias)
         K.layernorm(tok[:, 0], w["ln_w"], w["ln_b"], ws.cls[:n], eps)     # the class-token rows only: row stride S * D
         if self.kind == "clip":
             K.gemm(ws.cls, w["proj"], None, ws.proj)
