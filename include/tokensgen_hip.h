@@ -879,6 +879,32 @@ int tg_block_motion(const void* cur, long cur_so, long cur_si, const void* ref, 
 int tg_block_warp_sse(const void* cur, long a_so, long a_si, long a_sr, long a_sp, long a_sc, const void* ref, long b_so, long b_si, long b_sr, long b_sp, long b_sc,
                       const void* mv, int n_outer, int n_inner, int H, int W, int block, void* sse, void* sse0, int* status, hipStream_t stream);
 
+/* Motion-compensated interpolation of in-between frames, in integers (csrc/mci.hip; host side: tokensgen_amd/motion.py).  No reference code: these are
+ * the definitions.  Luma, blocks, Hb, Wb as above.
+ * Pairs and phases: a pair is (prev, next); factor n (2 <= n <= 8) asks for the n - 1 frames at phases k = 1 .. n - 1 between them.
+ * Fields: fwd = tg_block_motion of (prev -> next), bwd = tg_block_motion of (next -> prev), int16 [n_outer][n_inner][Hb][Wb][2].
+ * rnd(k, d, n) = floor((2 k d + n) / (2 n)): k d / n rounded, halves toward +infinity, d of either sign.
+ * Candidates of block (by, bx) of the in-between frame: (0, 0); fwd[y][x] for y in {by - 1, by, by + 1}, x in {bx - 1, bx, bx + 1} clamped to the grid; with bwd
+ *   also -bwd[y][x] over the same neighbourhood.  A candidate v = (dy, dx) is the whole motion prev -> next.  With a = (rnd(k, dy, n), rnd(k, dx, n)) its previous-frame
+ *   block starts at (by * block - a_y, bx * block - a_x) and its next-frame block at that point plus v.  It is admitted only if both blocks lie wholly inside the frame
+ *   ((0, 0) always is) and, for fields that are not a search's, |dy|, |dx| <= 32.
+ * Cost: bisad = sum over the two blocks of |Y_prev - Y_next| (at most 65 280).  The winner is the minimum of (bisad, dy^2 + dx^2, dy, dx) in lexicographic order.
+ * Render (overlapped block compensation), every pixel of the frame: for pixel row y, c = 2 y + 1 - block, r0 = floor(c / (2 block)), f = c - r0 * 2 block (odd, 1 ..
+ *   2 block - 1); block rows clamp(r0) and clamp(r0 + 1) (to 0 .. Hb - 1) weigh 2 block - f and f; columns alike.  For each of the four (row, column) choices with
+ *   that block's vector v and a: P = prev[clamp(y - a_y)][clamp(x - a_x)][ch], N = next[clamp(y - a_y + dy)][clamp(x - a_x + dx)][ch], coordinates clamped to the
+ *   frame (a neighbouring block's vector may point a border pixel outside it; whatever mvi holds, no address leaves the frame).
+ *   out = floor((sum wy wx ((n - k) P + k N) + D / 2) / D), D = n * 4 * block^2 (the sum is at most 255 D < 2^22).
+ * tg_mci_select: planes, pitch and plane strides as tg_block_motion (prev and next are usually two views of one stack of planes).  bwd may be NULL: forward candidates
+ *   only.  Outputs, contiguous: mvi int16 [n_outer][n_inner][n - 1][Hb][Wb][2], cost int32 [n_outer][n_inner][n - 1][Hb][Wb].  One launch for all pairs and phases,
+ *   no atomics, no workspace, bitwise reproducible.
+ * tg_mci_render: prev, next uint8 RGB with the strides of tg_luma_u8 (per input); mvi as above.  Frame k of pair (o, i) is written, interleaved [H][W][3], at
+ *   out + o * out_so + (i * n + k) * out_sf (bytes; out_sf >= 3 H W, out_so >= (n_inner * n + 1) * out_sf): out is the upsampled video [n_outer][n_inner * n + 1]
+ *   [H][W][3], whose frames i * n (the originals) the caller copies in. */
+int tg_mci_select(const void* prev, long prev_so, long prev_si, const void* next, long next_so, long next_si, const void* fwd, const void* bwd, int n_outer, int n_inner,
+                  int H, int W, long pitch, int block, int n, void* mvi, void* cost, hipStream_t stream);
+int tg_mci_render(const void* prev, long a_so, long a_si, long a_sr, long a_sp, long a_sc, const void* next, long b_so, long b_si, long b_sr, long b_sp, long b_sc,
+                  const void* mvi, int n_outer, int n_inner, int H, int W, int block, int n, void* out, long out_so, long out_sf, hipStream_t stream);
+
 /* Dispatch overrides for the cross-check tests — NOT part of the operator surface.  The library reads no environment variable and keeps no other
  * process-wide state: the defaults are the shipped path, and these knobs only choose between two PRODUCT kernels of the same operator (each pair is held
  * bitwise or to rounding against each other by tests/).  Knobs: TG_ATTN_PP_MIN_WG (1024: workgroups from which the 8-wave attention kernel is used),

@@ -1268,3 +1268,60 @@ def block_warp_sse(cur, ref, mv, block):
     L.check(_launch("block_warp_sse", L.load().tg_block_warp_sse, _p(cur), *sa, _p(ref), *sb, _p(mv), no, ni, H, W, block, _p(sse[0]), _p(sse[1]), _p(status),
                     _stream()), "tg_block_warp_sse")
     return sse[0], sse[1], status
+
+
+MCI_FACTORS = (2, 8)
+
+
+def _chk_planes(prev, nxt, width, block, who):
+    for t, name in ((prev, "prev"), (nxt, "next")):
+        _chk(t, name, torch.uint8)
+    if prev.dim() != 4 or prev.shape != nxt.shape or prev.stride()[2:] != (prev.shape[3], 1) or nxt.stride()[2:] != (nxt.shape[3], 1) or min(prev.stride() + nxt.stride()) < 0:
+        raise ValueError(f"{who}: expected two equally shaped stacks of packed planes [n_outer, n_inner, H, pitch], got {tuple(prev.shape)} and {tuple(nxt.shape)}")
+    no, ni, H, pitch = prev.shape
+    if block not in MOTION_BLOCKS or no * ni < 1 or not block <= int(width) <= pitch or H < block:
+        raise ValueError(f"{who}: block {block} (8 or 16), planes {tuple(prev.shape)} of width {width}")
+    return no, ni, H, pitch
+
+
+def mci_select(prev, nxt, fwd, bwd, width, block, factor):
+    """tg_mci_select: prev, nxt uint8 luma planes [n_outer, n_inner, H, pitch] from luma_u8 (views along the first two axes allowed); fwd, bwd int16
+    [n_outer, n_inner, Hb, Wb, 2] contiguous, the fields of block_motion(prev, nxt) and block_motion(nxt, prev) (bwd may be None).  Returns mvi int16
+    [n_outer, n_inner, factor - 1, Hb, Wb, 2] and cost int32 [n_outer, n_inner, factor - 1, Hb, Wb]."""
+    block, n, W = int(block), int(factor), int(width)
+    no, ni, H, pitch = _chk_planes(prev, nxt, W, block, "mci_select")
+    if not MCI_FACTORS[0] <= n <= MCI_FACTORS[1]:
+        raise ValueError(f"mci_select: factor must be in {MCI_FACTORS[0]}..{MCI_FACTORS[1]}, got {n}")
+    Hb, Wb = H // block, W // block
+    for t, name in ((fwd, "fwd"), (bwd, "bwd")):
+        if t is None and name == "bwd":
+            continue
+        _chk(t, name, torch.int16)
+        if tuple(t.shape) != (no, ni, Hb, Wb, 2) or not t.is_contiguous():
+            raise ValueError(f"mci_select: {name} must be contiguous [{no}, {ni}, {Hb}, {Wb}, 2], got {tuple(t.shape)}")
+    mvi = torch.empty(no, ni, n - 1, Hb, Wb, 2, dtype=torch.int16, device=prev.device)
+    cost = torch.empty(no, ni, n - 1, Hb, Wb, dtype=torch.int32, device=prev.device)
+    L.check(_launch("mci_select", L.load().tg_mci_select, _p(prev), prev.stride(0), prev.stride(1), _p(nxt), nxt.stride(0), nxt.stride(1), _p(fwd),
+                    None if bwd is None else _p(bwd), no, ni, H, W, pitch, block, n, _p(mvi), _p(cost), _stream()), "tg_mci_select")
+    return mvi, cost
+
+
+def mci_render(prev, nxt, mvi, block, factor, out):
+    """tg_mci_render: prev, nxt uint8 RGB frames of one shape ([B, P, H, W, 3], any views), mvi int16 [B, P, factor - 1, Hb, Wb, 2] contiguous; out uint8
+    [B, P * factor + 1, H, W, 3] contiguous: frame i * factor + k of out is written for every pair i and phase k = 1 .. factor - 1, the frames i * factor are left alone."""
+    _chk_frames(prev, "prev"); _chk_frames(nxt, "next"); _chk(mvi, "mvi", torch.int16); _chk_frames(out, "out")
+    block, n = int(block), int(factor)
+    if prev.dim() != 5 or prev.shape != nxt.shape or block not in MOTION_BLOCKS or not MCI_FACTORS[0] <= n <= MCI_FACTORS[1]:
+        raise ValueError(f"mci_render: frames {tuple(prev.shape)} and {tuple(nxt.shape)} ([B, P, H, W, 3]) with block {block}, factor {n}")
+    (no, ni, H, W), sa = _rgb_strides(prev)
+    _, sb = _rgb_strides(nxt)
+    if no * ni < 1 or H < block or W < block:
+        raise ValueError(f"mci_render: frames {tuple(prev.shape)} hold no {block} x {block} block")
+    Hb, Wb = H // block, W // block
+    if tuple(mvi.shape) != (no, ni, n - 1, Hb, Wb, 2) or not mvi.is_contiguous():
+        raise ValueError(f"mci_render: mvi must be contiguous [{no}, {ni}, {n - 1}, {Hb}, {Wb}, 2], got {tuple(mvi.shape)}")
+    if tuple(out.shape) != (no, ni * n + 1, H, W, 3) or not out.is_contiguous():
+        raise ValueError(f"mci_render: out must be contiguous [{no}, {ni * n + 1}, {H}, {W}, 3], got {tuple(out.shape)}")
+    L.check(_launch("mci_render", L.load().tg_mci_render, _p(prev), *sa, _p(nxt), *sb, _p(mvi), no, ni, H, W, block, n, _p(out), out.stride(0), out.stride(1),
+                    _stream()), "tg_mci_render")
+    return out

@@ -97,6 +97,8 @@ PROTOTYPES = {
     "tg_luma_u8": [_vp, _l, _l, _l, _l, _l, _i, _i, _i, _i, _vp, _vp],
     "tg_block_motion": [_vp, _l, _l, _vp, _l, _l, _i, _i, _i, _i, _l, _i, _i, _vp, _vp, _vp, _vp],
     "tg_block_warp_sse": [_vp, _l, _l, _l, _l, _l, _vp, _l, _l, _l, _l, _l, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "tg_mci_select": [_vp, _l, _l, _vp, _l, _l, _vp, _vp, _i, _i, _i, _i, _l, _i, _i, _vp, _vp, _vp],
+    "tg_mci_render": [_vp, _l, _l, _l, _l, _l, _vp, _l, _l, _l, _l, _l, _vp, _i, _i, _i, _i, _i, _i, _vp, _l, _l, _vp],
     "tg_conv3d_cl": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _l, _i, _i, _i, _vp, _vp, _vp, _vp],
     "tg_conv3d_up2_subpixel": [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _l, _i, _vp, _vp, _vp],
     "tg_groupnorm_finalize": [_vp, _l, _i, _f, _vp, _vp],

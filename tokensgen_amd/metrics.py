@@ -25,6 +25,7 @@ the background model's features, which are computed once per clip either way (DE
 `video_motion` / `video_warp_error` / `VideoMotion` measure what the figures above do not, motion: exhaustive integer block matching on 8-bit luma
 (tokensgen_amd.motion; tg_block_motion, csrc/motion.hip) gives per frame pair the motion magnitude, its top-fraction mean ("dynamic degree"), the share of still
 blocks, flicker and the motion-compensated residual, and the warping error of a video under its own vectors or under those of an edit's source.
+`video_motion_smoothness` holds out every other frame and asks how well motion-compensated interpolation (motion.interpolate_frames) predicts it.
 
 Not here: `calculate_delta_Eab` (cv2.cvtColor's 8-bit Lab, source absent), the numpy / skimage variants, learned optical flow.  Not registered under the `longvgen`
 alias (tokensgen_amd.compat carries hot-path names only).  There is no CPU path."""
@@ -319,6 +320,37 @@ def video_warp_error(frames, motion_from=None, block=16, radius=16):
     w = M.warp_sse(frames, mv)
     out = _warp_pooled(_warp_curves(w["sse"], w["sse0"], block))
     out["status"] = w["status"]
+    return out
+
+
+def video_motion_smoothness(frames, block=16, radius=16):
+    """Motion smoothness, the VBench way with the project's own interpolator: drop every other frame, interpolate the dropped frames back from their two neighbours
+    (motion.interpolate_frames, factor 2) and compare with the truth.  frames: uint8 [F, H, W, 3] or [B, T, H, W, 3], at least 3 frames (and at least 11 x 11
+    pixels, video_metrics' window); the frames used are 0, 2, 4, .. and the held-out ones 1, 3, .. below the last used one.  Returns float64 device tensors: per
+    held-out frame ([M] / [B, M], M = (T - 1) // 2) "mc_mse" / "mc_psnr" of the motion-compensated frame and "blend_mse" / "blend_psnr" of the plain average
+    (a + b + 1) >> 1 of the two neighbours (video_metrics' mse and psnr = 10 log10(1 / (mse + 1e-8))); the pooled 0-dim "mc_mse_mean", "mc_psnr_pooled",
+    "blend_mse_mean", "blend_psnr_pooled" (the PSNR of the mean mse); and 0-dim "score" = 1 - mean |mc - truth| / 255 over all held-out bytes.  A video that moves
+    smoothly is predictable from every other frame: mc_psnr high and well above blend_psnr.  The average and the absolute difference are torch arithmetic on the
+    held-out frames; nothing here waits for the device."""
+    M.check_frames(frames, "video_motion_smoothness")
+    M.check_block(block, radius, frames.shape[-3], frames.shape[-2], "video_motion_smoothness")
+    T = frames.shape[-4]
+    if T < 3:
+        raise ValueError(f"video_motion_smoothness: {T} frames hold out none; pass at least 3")
+    if min(frames.shape[-3], frames.shape[-2]) < WINDOW:
+        raise ValueError(f"video_motion_smoothness: frames of {frames.shape[-3]} x {frames.shape[-2]} are smaller than video_metrics' {WINDOW} x {WINDOW} window")
+    m = (T - 1) // 2
+    kept = frames[..., 0:2 * m + 1:2, :, :, :]
+    truth = frames[..., 1:2 * m:2, :, :, :]
+    mc = M.interpolate_frames(kept, 2, block, radius)[..., 1::2, :, :, :]
+    a, b = kept[..., :-1, :, :, :].to(torch.int16), kept[..., 1:, :, :, :].to(torch.int16)
+    avg = ((a + b + 1) >> 1).to(torch.uint8)
+    out = {}
+    for name, guess in (("mc", mc), ("blend", avg)):
+        r = video_metrics(guess, truth)
+        out.update({f"{name}_mse": r["mse"], f"{name}_psnr": r["psnr"], f"{name}_mse_mean": r["mse"].mean(), f"{name}_psnr_pooled": r["psnr_pooled"]})
+    diff = (mc.to(torch.int16) - truth.to(torch.int16)).abs().sum(dtype=torch.int64)
+    out["score"] = 1.0 - diff.to(torch.float64) / (255.0 * truth.numel())
     return out
 
 

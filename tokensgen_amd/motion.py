@@ -7,6 +7,9 @@ of the kernels is an exact integer, so a test is `torch.equal`.
 Frames are the uint8 output of video_io, [F, H, W, 3] or [B, T, H, W, 3] (views allowed).  Pairs are (t, t + 1) inside each batch item; with `ref` (same shape)
 frame t of `frames` is paired with frame t of `ref`.  The vector (dy, dx) of a block says: the block at (y, x) of the first frame of the pair matches
 (y + dy, x + dx) of the second.  `summarize` is plain torch arithmetic on the small per-block results and runs on any device; the search has no CPU path.
+
+`interpolate_frames` / `FrameRateUpsampler` use those vectors to make frames: motion-compensated interpolation of the in-between frames of every pair, for an
+integer frame-rate factor 2 .. 8 (tg_mci_select, tg_mci_render, csrc/mci.hip), exact integers as well.
 Not registered under the `longvgen` alias."""
 import math
 
@@ -14,7 +17,7 @@ import torch
 
 from . import kernels as K
 
-BLOCKS, MAX_RADIUS = K.MOTION_BLOCKS, K.MOTION_MAX_RADIUS
+BLOCKS, MAX_RADIUS, FACTORS = K.MOTION_BLOCKS, K.MOTION_MAX_RADIUS, K.MCI_FACTORS
 
 
 def check_frames(frames, who, ref=None, pairs_within=True):
@@ -88,6 +91,65 @@ def warp_sse(frames, mv, ref=None):
     if frames.dim() == 4:
         sse, sse0 = sse[0], sse0[0]
     return {"sse": sse, "sse0": sse0, "status": status}
+
+
+def check_factor(factor, who):
+    if not isinstance(factor, int) or isinstance(factor, bool) or not FACTORS[0] <= factor <= FACTORS[1]:
+        raise ValueError(f"{who}: factor must be an integer in {FACTORS[0]}..{FACTORS[1]}, got {factor!r}")
+
+
+def interpolate_frames(frames, factor=2, block=16, radius=16, bidirectional=True, return_vectors=False):
+    """Motion-compensated frame-rate upsampling.  frames: uint8 [F, H, W, 3] or [B, T, H, W, 3] (any view), at least 2 frames.  Returns the uint8 video
+    [.., (T - 1) * factor + 1, H, W, 3]: original frame t sits at index t * factor byte for byte, frame t * factor + k is the phase-k frame of pair (t, t + 1) and
+    depends on that pair's two frames alone.  The vectors of block_motion (prev -> next and, with `bidirectional`, next -> prev) give every block of an in-between
+    frame its candidates; tg_mci_select picks one by the bilateral SAD, tg_mci_render blends the overlapping block predictions.  With return_vectors a dict
+    {"video", "mvi": int16 [.., P, factor - 1, Hb, Wb, 2], "cost": int32 [.., P, factor - 1, Hb, Wb]}.  Nothing here waits for the device."""
+    P = check_frames(frames, "interpolate_frames")
+    H, W = frames.shape[-3], frames.shape[-2]
+    check_factor(factor, "interpolate_frames")
+    check_block(block, radius, H, W, "interpolate_frames")
+    f5 = frames if frames.dim() == 5 else frames[None]
+    ya = K.luma_u8(f5)
+    prev, nxt = ya[:, :-1], ya[:, 1:]
+    fwd = K.block_motion(prev, nxt, W, block, radius)[0]
+    bwd = K.block_motion(nxt, prev, W, block, radius)[0] if bidirectional else None
+    mvi, cost = K.mci_select(prev, nxt, fwd, bwd, W, block, factor)
+    video = torch.empty(f5.shape[0], P * factor + 1, H, W, 3, dtype=torch.uint8, device=frames.device)
+    video[:, ::factor] = f5                                               # the originals: one strided copy
+    K.mci_render(f5[:, :-1], f5[:, 1:], mvi, block, factor, video)
+    if frames.dim() == 4:
+        video, mvi, cost = video[0], mvi[0], cost[0]
+    return {"video": video, "mvi": mvi, "cost": cost} if return_vectors else video
+
+
+class FrameRateUpsampler:
+    """interpolate_frames for a long video that arrives clip by clip (the FIFO result).  `update(frames)` continues the current video with a clip, uint8 [F, H, W, 3]
+    (F >= 1), and returns the frames that became final: the in-between frames that lead from the last frame of the previous clip (carried on the device) to this
+    clip, and this clip upsampled; the very first frame of a video comes with its first clip.  `new_video()` forgets the carried frame.  Every pair's frames come
+    from its two frames alone: the pieces concatenate to the bits of one interpolate_frames call on the whole video.  Nothing waits for the device."""
+
+    def __init__(self, factor=2, block=16, radius=16, bidirectional=True):
+        check_factor(factor, "FrameRateUpsampler")
+        check_block(block, radius, block, block, "FrameRateUpsampler")
+        self.factor, self.block, self.radius, self.bidirectional = factor, block, radius, bool(bidirectional)
+        self._last = None
+
+    def update(self, frames):
+        if isinstance(frames, torch.Tensor) and frames.dim() != 4:
+            raise ValueError(f"FrameRateUpsampler.update: one video's clip [F, H, W, 3], got {tuple(frames.shape)}")
+        check_frames(frames, "FrameRateUpsampler.update", pairs_within=False)
+        check_block(self.block, self.radius, frames.shape[1], frames.shape[2], "FrameRateUpsampler.update")
+        if self._last is not None and self._last.shape[1:] != frames.shape[1:]:
+            raise ValueError(f"FrameRateUpsampler.update: the video's frames are {tuple(self._last.shape[1:])}, this clip's {tuple(frames.shape[1:])}")
+        seq = frames if self._last is None else torch.cat([self._last, frames])
+        out = seq.clone() if seq.shape[0] < 2 else interpolate_frames(seq, self.factor, self.block, self.radius, self.bidirectional)
+        if self._last is not None:
+            out = out[1:]                                                 # the carried frame was returned with its own clip
+        self._last = frames[-1:].clone()
+        return out
+
+    def new_video(self):
+        self._last = None
 
 
 def top_count(top_fraction, blocks):

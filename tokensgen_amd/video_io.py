@@ -185,19 +185,40 @@ def frames_to_uint8(video, layout="bcthw", rounding=0):
 
 class VideoProcessor:
     """`pipe.video_processor = VideoProcessor()`: the post-processing the reference pipeline's attribute of that name does (diffusers 0.31 VideoProcessor, restated,
-    source absent).  The pipeline carries none by default: the FIFO driver then returns the decoded bf16 [B, 3, T, H, W] as before."""
+    source absent).  The pipeline carries none by default: the FIFO driver then returns the decoded bf16 [B, 3, T, H, W] as before.
+
+    frame_rate_factor n > 1 (2 .. 8; not in diffusers) raises the frame rate of the byte outputs by motion-compensated interpolation on the device
+    (tokensgen_amd.motion.interpolate_frames with `block`, `radius`, `bidirectional`): T frames become (T - 1) n + 1, the originals unchanged at
+    every n-th place, and the caller writes them at `fps = output_fps * n`.  With the default, 1, every output is what it was and the motion code is never imported."""
+
+    def __init__(self, frame_rate_factor=1, block=16, radius=16, bidirectional=True):
+        if not isinstance(frame_rate_factor, int) or isinstance(frame_rate_factor, bool) or not 1 <= frame_rate_factor <= 8:
+            raise ValueError(f"VideoProcessor: frame_rate_factor must be an integer in 1..8, got {frame_rate_factor!r}")
+        self.frame_rate_factor, self.block, self.radius, self.bidirectional = frame_rate_factor, block, radius, bidirectional
+        if frame_rate_factor > 1:
+            from . import motion
+            motion.check_block(block, radius, block, block, "VideoProcessor")
+
+    def _upsample(self, frames_u8):
+        if self.frame_rate_factor == 1:
+            return frames_u8
+        from .motion import interpolate_frames
+        return interpolate_frames(frames_u8, self.frame_rate_factor, self.block, self.radius, self.bidirectional)
 
     def postprocess_video(self, video, output_type="np"):
         """video bf16 [B, 3, T, H, W] in [-1, 1].  "pt": [B, T, 3, H, W] in the input dtype, in [0, 1]; "np": float32 numpy [B, T, H, W, 3] in [0, 1]; "pil": B lists of T
-        PIL images (rounded half to even); "uint8": uint8 tensor [B, T, H, W, 3] on the device, truncated: `(np_output * 255).astype(uint8)` byte for byte."""
+        PIL images (rounded half to even); "uint8": uint8 tensor [B, T, H, W, 3] on the device, truncated: `(np_output * 255).astype(uint8)` byte for byte.
+        With frame_rate_factor > 1 "uint8" is interpolated, "pil" is interpolated from its rounded bytes, and the float outputs are refused."""
+        if output_type in ("pt", "np") and self.frame_rate_factor > 1:
+            raise ValueError(f"frame_rate_factor {self.frame_rate_factor} interpolates bytes: ask for output_type \"uint8\" (or \"pil\"), not {output_type!r}")
         if output_type == "pt":
             return K.video_to_uint8(video, 1, K.VIDEO_BF16_PLANAR)
         if output_type == "np":
             return K.video_to_uint8(video, 1, K.VIDEO_F32).cpu().numpy()
         if output_type == "uint8":
-            return K.video_to_uint8(video, 1, K.VIDEO_U8, 0)
+            return self._upsample(K.video_to_uint8(video, 1, K.VIDEO_U8, 0))
         if output_type == "pil":
             from PIL import Image
-            by = K.video_to_uint8(video, 1, K.VIDEO_U8, 1).cpu().numpy()
+            by = self._upsample(K.video_to_uint8(video, 1, K.VIDEO_U8, 1)).cpu().numpy()
             return [[Image.fromarray(frame) for frame in clip] for clip in by]
         raise ValueError(f"output_type must be one of 'pt', 'np', 'pil', 'uint8'; got {output_type!r}")
