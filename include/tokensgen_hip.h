@@ -905,6 +905,44 @@ int tg_mci_select(const void* prev, long prev_so, long prev_si, const void* next
 int tg_mci_render(const void* prev, long a_so, long a_si, long a_sr, long a_sp, long a_sc, const void* next, long b_so, long b_si, long b_sr, long b_sp, long b_sc,
                   const void* mvi, int n_outer, int n_inner, int H, int W, int block, int n, void* out, long out_so, long out_sf, hipStream_t stream);
 
+/* Colour of the byte output: histograms, colour matching against an anchor by per-frame lookup tables, and CIE L*a*b* sums (csrc/color.hip; host side:
+ * tokensgen_amd/color.py and metrics.py).  The matching has no reference code: these are the definitions.  The Lab sums serve calculate_delta_Eab of
+ * longvgen/metrics/psnr_ssim.py:298-333 on the true L*a*b* scale (the stated deviation of §8j).
+ * tg_color_hist_u8: hist[f][c][v] (int32 [F][3][256]) = the number of pixels of frame f whose channel c is v; src contiguous uint8 [F][H][W][3], H W < 2^31.  Two
+ *   launches on `stream` (the output's zeroing, then the counts by integer atomics: exact, order-independent); a frame's counts depend on that frame's bytes alone.
+ *   tg_color_strip_bytes(0) is the bytes of a frame one workgroup counts (tg_color_strip_bytes(1): that tg_color_apply_lut maps), for tests that want several.
+ * tg_color_match_lut: lut[f][c][v] (uint8 [F][3][256]) maps channel c of frame f towards the anchor.  Source histogram of frame t: S_t = sum of hist_k over
+ *   k = max(0, t - window + 1) .. t in int64, k counted from the start of the video: hist (int32 [F][3][256]) holds the call's frames, history (int32
+ *   [n_history][3][256], 0 <= n_history < window, NULL with 0) the n_history frames before them, oldest first; fewer carried frames than window - 1 mean the video
+ *   starts there.  anchor: int64 [3][256].  1 <= window <= 64, 0 <= strength <= 1, max_gain >= 1.
+ *   mode 0 (meanstd): from a histogram n = sum S[v], s1 = sum v S[v], s2 = sum v^2 S[v] in integers; mean = double(s1) / double(n), ex2 = double(s2) / double(n),
+ *     var = max(ex2 - mean * mean, 0), std = sqrt(var), each operation rounded by itself; g = std_ref / std_src if std_src > 0 else 1, clamped to [1 / max_gain,
+ *     max_gain]; g' = 1 + strength (g - 1), m' = mean_src + strength (mean_ref - mean_src); lut[v] = clamp(rint((v - mean_src) g' + m'), 0, 255), halves to even.
+ *   mode 1 (histogram): cs, cr the cumulative sums of S_t and the anchor, ns = cs[255], nr = cr[255]; m[v] = min{u : cr[u] ns >= cs[v] nr} in 64-bit integers;
+ *     lut[v] = clamp(rint(v + strength (m[v] - v)), 0, 255).
+ *   A histogram (source window or anchor) with a negative count or a total outside 1 .. 2^31 - 1 is refused ON THE DEVICE: its table is the identity and the
+ *   caller-owned DEVICE word status[0] is incremented by one (the caller zeroes it; the convention of tg_text_embed).  hist, history, status 4-byte aligned, anchor 8.
+ * tg_color_apply_lut: dst[f][y][x][c] = lut[f][c][src[f][y][x][c]], src and dst contiguous uint8 [F][H][W][3], H W < 2^31; dst == src is allowed, any other
+ *   overlap is TG_ERR_ARG.  lut 4-byte aligned.  One launch.
+ * tg_lab_metrics: per frame (image = outer * n_inner + inner) float64 sums over the h x w pixels of input a: out[image] = {sum L, sum a, sum b, sum C}; with a second
+ *   input b (may be NULL) out[image] = {the four sums of a, the four sums of b, sum dE}, dE = sqrt(dL^2 + da^2 + db^2) (CIE76): 4 or 9 doubles per frame.  Addressing,
+ *   dtype and alignment as tg_image_metrics with three channels (a_sc is the stride from R to G to B); h, w >= 1.  Per pixel and channel c = v / 255 (uint8) or the
+ *   value clamped to [0, 1] (a NaN counts as 0); lin = c / 12.92 if c <= 0.04045 else ((c + 0.055) / 1.055)^2.4; X = (0.412453 R + 0.357580 G + 0.180423 B) /
+ *   0.950456, Y = 0.212671 R + 0.715160 G + 0.072169 B, Z = (0.019334 R + 0.119193 G + 0.950227 B) / 1.088754; f(t) = cbrt(t) if t > 0.008856 else 7.787 t +
+ *   16 / 116; L = 116 cbrt(Y) - 16 if Y > 0.008856 else 903.3 Y, a = 500 (f(X) - f(Y)), b = 200 (f(Y) - f(Z)), C = sqrt(a^2 + b^2).  All float64, no fused
+ *   multiply-add.  ws: tg_lab_metrics_ws_doubles(frames, h, w, b != NULL) doubles (4 or 9 per tile of tg_lab_metrics_tile(0) x tg_lab_metrics_tile(1) pixels).
+ *   Two launches on `stream` (tiles, then the sum of a frame's tiles in tile order), no atomics: bitwise reproducible, a frame's sums do not depend on the
+ *   number of frames or on its place among them; identical inputs give sum dE == 0 exactly. */
+long tg_color_strip_bytes(int which);
+int tg_color_hist_u8(const void* src, int F, int H, int W, void* hist, hipStream_t stream);
+int tg_color_match_lut(const void* hist, int F, const void* history, int n_history, const void* anchor, int mode, double strength, int window, double max_gain,
+                       void* lut, int* status, hipStream_t stream);
+int tg_color_apply_lut(const void* src, const void* lut, int F, int H, int W, void* dst, hipStream_t stream);
+long tg_lab_metrics_tile(int axis);
+long tg_lab_metrics_ws_doubles(long frames, int h, int w, int two);
+int tg_lab_metrics(const void* a, long a_so, long a_si, long a_sc, long a_sr, long a_sp, const void* b, long b_so, long b_si, long b_sc, long b_sr, long b_sp,
+                   int dtype, int n_outer, int n_inner, int h, int w, double* ws, double* out, hipStream_t stream);
+
 /* Dispatch overrides for the cross-check tests — NOT part of the operator surface.  The library reads no environment variable and keeps no other
  * process-wide state: the defaults are the shipped path, and these knobs only choose between two PRODUCT kernels of the same operator (each pair is held
  * bitwise or to rounding against each other by tests/).  Knobs: TG_ATTN_PP_MIN_WG (1024: workgroups from which the 8-wave attention kernel is used),

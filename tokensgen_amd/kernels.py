@@ -1325,3 +1325,106 @@ def mci_render(prev, nxt, mvi, block, factor, out):
     L.check(_launch("mci_render", L.load().tg_mci_render, _p(prev), *sa, _p(nxt), *sb, _p(mvi), no, ni, H, W, block, n, _p(out), out.stride(0), out.stride(1),
                     _stream()), "tg_mci_render")
     return out
+
+
+COLOR_MODES = {"meanstd": 0, "histogram": 1}
+COLOR_MAX_WINDOW = 64
+
+
+def _chk_u8_frames(t, name):
+    """contiguous uint8 [F, H, W, 3] on the GPU -> (F, H, W)"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{name}: expected a GPU tensor (tokensgen_amd has no CPU fallback)")
+    if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[-1] != 3 or not t.is_contiguous() or t.numel() < 1:
+        raise ValueError(f"{name}: expected contiguous uint8 [F, H, W, 3] with at least one pixel, got {t.dtype} {tuple(t.shape)}")
+    if t.shape[1] * t.shape[2] >= 1 << 31:
+        raise ValueError(f"{name}: a frame of {t.shape[1]} x {t.shape[2]} pixels reaches 2^31")
+    return t.shape[0], t.shape[1], t.shape[2]
+
+
+def color_hist_u8(frames):
+    """tg_color_hist_u8: contiguous uint8 [F, H, W, 3] -> int32 [F, 3, 256], the counts per frame, channel and value (exact; a frame's counts depend on it alone)."""
+    F, H, W = _chk_u8_frames(frames, "color_hist_u8")
+    out = torch.empty(F, 3, 256, dtype=torch.int32, device=frames.device)
+    L.check(_launch("color_hist_u8", L.load().tg_color_hist_u8, _p(frames), F, H, W, _p(out), _stream()), "tg_color_hist_u8")
+    return out
+
+
+def color_match_lut(hist, anchor, mode, strength, window, max_gain, history=None, status=None):
+    """tg_color_match_lut: hist int32 [F, 3, 256], anchor int64 [3, 256], history None or int32 [n, 3, 256] (the n < window frames before the call's, oldest first)
+    -> (lut uint8 [F, 3, 256], status int32 [1]: the number of (frame, channel) histograms the device refused and gave the identity table)."""
+    _chk(hist, "hist", torch.int32); _chk(anchor, "anchor", torch.int64)
+    if hist.dim() != 3 or tuple(hist.shape[1:]) != (3, 256) or hist.shape[0] < 1 or not hist.is_contiguous():
+        raise ValueError(f"color_match_lut: hist must be contiguous [F, 3, 256], got {tuple(hist.shape)}")
+    if tuple(anchor.shape) != (3, 256) or not anchor.is_contiguous():
+        raise ValueError(f"color_match_lut: anchor must be contiguous [3, 256], got {tuple(anchor.shape)}")
+    n_hist = 0
+    if history is not None and history.shape[0] > 0:
+        _chk(history, "history", torch.int32)
+        if history.dim() != 3 or tuple(history.shape[1:]) != (3, 256) or not history.is_contiguous() or history.shape[0] >= window:
+            raise ValueError(f"color_match_lut: history must be contiguous [n, 3, 256] with n < window = {window}, got {tuple(history.shape)}")
+        n_hist = history.shape[0]
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=hist.device)
+    else:
+        _chk(status, "status", torch.int32)
+    lut = torch.empty(hist.shape[0], 3, 256, dtype=torch.uint8, device=hist.device)
+    L.check(_launch("color_match_lut", L.load().tg_color_match_lut, _p(hist), hist.shape[0], _p(history) if n_hist else None, n_hist, _p(anchor), COLOR_MODES[mode],
+                    float(strength), int(window), float(max_gain), _p(lut), _p(status), _stream()), "tg_color_match_lut")
+    return lut, status
+
+
+def color_apply_lut(frames, lut, out=None):
+    """tg_color_apply_lut: out[f, y, x, c] = lut[f, c, frames[f, y, x, c]]; frames contiguous uint8 [F, H, W, 3], lut uint8 [F, 3, 256] contiguous; out None (a new
+    tensor), `frames` itself (in place) or another contiguous tensor of its shape."""
+    F, H, W = _chk_u8_frames(frames, "color_apply_lut")
+    _chk(lut, "lut", torch.uint8)
+    if tuple(lut.shape) != (F, 3, 256) or not lut.is_contiguous():
+        raise ValueError(f"color_apply_lut: lut must be contiguous [{F}, 3, 256], got {tuple(lut.shape)}")
+    if out is None:
+        out = torch.empty_like(frames)
+    elif _chk_u8_frames(out, "color_apply_lut: out") != (F, H, W) or out.device != frames.device:
+        raise ValueError(f"color_apply_lut: out must have the frames' shape {tuple(frames.shape)} and device, got {tuple(out.shape)}")
+    L.check(_launch("color_apply_lut", L.load().tg_color_apply_lut, _p(frames), _p(lut), F, H, W, _p(out), _stream()), "tg_color_apply_lut")
+    return out
+
+
+def lab_metrics(a, b, layout, crop_border=0):
+    """tg_lab_metrics: per frame of one (b None) or two equally shaped uint8 (0..255), fp32 or bf16 (in [0, 1]) RGB image batches the float64 sums over the h x w pixels
+    (the plane without `crop_border` pixels on every side) of CIE L*, a*, b*, C*ab of `a` -> [n_outer, n_inner, 4], and with b also those of b and of the CIE76
+    dE between them -> [n_outer, n_inner, 9].  layout, views and the crop as image_metrics; a frame's sums do not depend on the other frames of the call."""
+    for t, name in ((a, "a"), (b, "b")):
+        if t is None and name == "b":
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: expected a tensor")
+        if t.dtype not in _IMAGE_DTYPES:
+            raise TypeError(f"{name}: expected uint8, float32 or bfloat16, got {t.dtype}")
+    if b is not None and a.dtype != b.dtype:
+        raise TypeError(f"a and b must have one dtype, got {a.dtype} and {b.dtype}")
+    if layout not in IMAGE_LAYOUTS:
+        raise ValueError(f"layout must be one of {sorted(IMAGE_LAYOUTS)}, got {layout!r}")
+    if b is not None and a.shape != b.shape:
+        raise ValueError(f"image shapes are different: {tuple(a.shape)}, {tuple(b.shape)}")
+    (n_outer, n_inner, Cn, H, W), sa = _image_strides(a, layout)
+    sb = _image_strides(b, layout)[1] if b is not None else (0, 0, 0, 0, 0)
+    if Cn != 3:
+        raise ValueError(f"expected 3 channels (RGB), got {Cn}")
+    cb = int(crop_border)
+    h, w = H - 2 * cb, W - 2 * cb
+    if cb < 0 or h < 1 or w < 1:
+        raise ValueError(f"a {H} x {W} plane with crop_border {cb} has no pixel left")
+    if n_outer * n_inner < 1:
+        raise ValueError("no images")
+    if min(sa + sb) < 0:
+        raise ValueError("views with negative strides are not supported")
+    if not a.is_cuda or (b is not None and (not b.is_cuda or a.device != b.device)):
+        raise RuntimeError("lab_metrics: expected tensors on one GPU (tokensgen_amd has no CPU fallback)")
+    lib = L.load()
+    ns = 4 if b is None else 9
+    ws = torch.empty(lib.tg_lab_metrics_ws_doubles(n_outer * n_inner, h, w, int(b is not None)), dtype=torch.float64, device=a.device)
+    out = torch.empty(n_outer, n_inner, ns, dtype=torch.float64, device=a.device)
+    pa = a.data_ptr() + cb * (sa[3] + sa[4]) * a.element_size()
+    pb = None if b is None else b.data_ptr() + cb * (sb[3] + sb[4]) * b.element_size()
+    L.check(_launch("lab_metrics", lib.tg_lab_metrics, pa, *sa, pb, *sb, _IMAGE_DTYPES[a.dtype], n_outer, n_inner, h, w, _p(ws), _p(out), _stream()), "tg_lab_metrics")
+    return out

@@ -99,6 +99,10 @@ PROTOTYPES = {
     "tg_block_warp_sse": [_vp, _l, _l, _l, _l, _l, _vp, _l, _l, _l, _l, _l, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
     "tg_mci_select": [_vp, _l, _l, _vp, _l, _l, _vp, _vp, _i, _i, _i, _i, _l, _i, _i, _vp, _vp, _vp],
     "tg_mci_render": [_vp, _l, _l, _l, _l, _l, _vp, _l, _l, _l, _l, _l, _vp, _i, _i, _i, _i, _i, _i, _vp, _l, _l, _vp],
+    "tg_color_hist_u8": [_vp, _i, _i, _i, _vp, _vp],
+    "tg_color_match_lut": [_vp, _i, _vp, _i, _vp, _i, _d, _i, _d, _vp, _vp, _vp],
+    "tg_color_apply_lut": [_vp, _vp, _i, _i, _i, _vp, _vp],
+    "tg_lab_metrics": [_vp, _l, _l, _l, _l, _l, _vp, _l, _l, _l, _l, _l, _i, _i, _i, _i, _i, _vp, _vp, _vp],
     "tg_conv3d_cl": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _l, _i, _i, _i, _vp, _vp, _vp, _vp],
     "tg_conv3d_up2_subpixel": [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _l, _i, _vp, _vp, _vp],
     "tg_groupnorm_finalize": [_vp, _l, _i, _f, _vp, _vp],
@@ -142,6 +146,9 @@ QUERIES = {
     "tg_image_metrics_ws_doubles": [C.c_long, C.c_int, C.c_int],
     "tg_lpips_head_ws_doubles": [C.c_int, C.c_int, C.c_int],
     "tg_luma_pitch": [C.c_int],
+    "tg_color_strip_bytes": [C.c_int],
+    "tg_lab_metrics_tile": [C.c_int],
+    "tg_lab_metrics_ws_doubles": [C.c_long, C.c_int, C.c_int, C.c_int],
 }
 
 TG_BWD_ONE_KERNEL = 1

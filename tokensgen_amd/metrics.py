@@ -27,7 +27,13 @@ the background model's features, which are computed once per clip either way (DE
 blocks, flicker and the motion-compensated residual, and the warping error of a video under its own vectors or under those of an edit's source.
 `video_motion_smoothness` holds out every other frame and asks how well motion-compensated interpolation (motion.interpolate_frames) predicts it.
 
-Not here: `calculate_delta_Eab` (cv2.cvtColor's 8-bit Lab, source absent), the numpy / skimage variants, learned optical flow.  Not registered under the `longvgen`
+`calculate_delta_Eab` / `video_delta_eab` / `VideoMetrics().delta_eab = True` give the CIE76 colour difference of two videos, and `video_color_drift` /
+`VideoColorDrift` how far one video's mean L*a*b* and chroma wander from its first frames (tg_lab_metrics, csrc/color.hip).  STATED DEVIATION: the
+reference's `calculate_delta_Eab` (psnr_ssim.py:298-333) calls cv2.cvtColor on whatever it gets, which for uint8 is OpenCV's 8-bit Lab (L scaled by 255 / 100, a and
+b offset by 128, rounded to integers; cv2 is absent and that table-driven path cannot be restated from documentation); here dE is on the true L*a*b* scale, from
+OpenCV's documented floating-point formula and coefficients in float64.
+
+Not here: the numpy / skimage variants, learned optical flow.  Not registered under the `longvgen`
 alias (tokensgen_amd.compat carries hot-path names only).  There is no CPU path."""
 import torch
 
@@ -104,11 +110,15 @@ def calculate_lpips(img, img2, crop_border, input_order='CHW', test_y_channel=Fa
 class VideoMetrics:
     """Running PSNR / SSIM over many clips (a 25-clip evaluation): `update(a, b)` per clip launches and returns at once, `finalize()` pools every frame seen.
     Two updates give what one video_metrics call on the concatenated frames gives.  With lpips_model (a tokensgen_amd.lpips.LPIPS) both also carry "lpips" per frame
-    and "lpips_pooled", the mean over the frames (lpips.video_lpips); without one every key and value is what it was."""
+    and "lpips_pooled", the mean over the frames (lpips.video_lpips); without one every key and value is what it was.  With the attribute `delta_eab`
+    set to True before the first update (the constructor's parameter list stays what it was) both also carry "delta_eab" per frame and "delta_eab_pooled", their mean
+    (video_delta_eab; colour, so test_y_channel does not apply to it); with the default, False, nothing changes."""
+
+    delta_eab = False          # an attribute, set before the first update: `vm = VideoMetrics(...); vm.delta_eab = True`
 
     def __init__(self, crop_border=0, test_y_channel=False, lpips_model=None):
         self.crop_border, self.test_y_channel, self.lpips_model = crop_border, test_y_channel, lpips_model
-        self._mse, self._ssim, self._lpips = [], [], []
+        self._mse, self._ssim, self._lpips, self._eab = [], [], [], []
 
     def update(self, a, b):
         m = video_metrics(a, b, self.crop_border, self.test_y_channel)
@@ -119,6 +129,10 @@ class VideoMetrics:
             lp = video_lpips(a, b, self.lpips_model, self.crop_border)
             m["lpips"], m["lpips_pooled"] = lp["lpips"], lp["lpips_pooled"]
             self._lpips.append(lp["lpips"].reshape(-1))
+        if self.delta_eab:
+            de = video_delta_eab(a, b, self.crop_border)
+            m["delta_eab"], m["delta_eab_pooled"] = de["per_frame"], de["delta_eab"]
+            self._eab.append(de["per_frame"].reshape(-1))
         return m
 
     def finalize(self):
@@ -131,6 +145,9 @@ class VideoMetrics:
         if self.lpips_model is not None:
             out["lpips"] = torch.cat(self._lpips)
             out["lpips_pooled"] = out["lpips"].mean()
+        if self.delta_eab:
+            out["delta_eab"] = torch.cat(self._eab)
+            out["delta_eab_pooled"] = out["delta_eab"].mean()
         return out
 
 
@@ -416,4 +433,115 @@ class VideoMotion:
                 continue
             out[f"{k}_mean"] = torch.stack([v[k].mean() for v in self._videos])
         out["warp_psnr_pooled"], out["still_psnr_pooled"] = _psnr(out["warp_mse_mean"]), _psnr(out["still_mse_mean"])
+        return out
+
+
+def _lab_hw(t, crop_border):
+    hw = t.shape[-3:-1] if t.dtype == torch.uint8 else t.shape[-2:]
+    return (hw[0] - 2 * int(crop_border)) * (hw[1] - 2 * int(crop_border))
+
+
+def video_delta_eab(a, b, crop_border=0):
+    """CIE76 colour difference dE*ab of two equally shaped RGB videos on the GPU, from one tg_lab_metrics call.  a, b: the layouts of video_metrics with three
+    channels.  Returns float64 device tensors: "per_frame", each frame's mean over its pixels of sqrt(dL^2 + da^2 + db^2), shaped [B, T] / [F] / [n], and the 0-dim
+    "delta_eab", their mean.  L*a*b* is OpenCV's documented floating-point RGB2Lab on the true scale (the module's stated deviation).  A frame's figure does not
+    depend on the other frames of the call; identical inputs give exactly 0.  Nothing here waits for the device."""
+    assert isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor) and a.shape == b.shape, \
+        f"Image shapes are different: {getattr(a, 'shape', None)}, {getattr(b, 'shape', None)}."
+    out = K.lab_metrics(a, b, _layout(a), crop_border)                                  # [n_outer, n_inner, 9]
+    if a.dim() == 4:
+        out = out[0]
+    per_frame = out[..., 8] / _lab_hw(a, crop_border)
+    return {"per_frame": per_frame, "delta_eab": per_frame.mean()}
+
+
+def calculate_delta_Eab(img, img2, crop_border, input_order='HWC', test_y_channel=False, **kwargs):
+    """psnr_ssim.py:298-333 for ONE pair of GPU images, (h, w, 3) with 'HWC' or (3, h, w) with 'CHW': uint8 (0..255), or fp32 / bf16 in [0, 1]; the mean over the
+    pixels of the CIE76 dE as a 0-dim float64 device tensor, on the true L*a*b* scale (the module's stated deviation).  test_y_channel=True raises ValueError:
+    the reference hands a one-channel image to cvtColor(RGB2LAB), which fails there too."""
+    assert img.shape == img2.shape, (f'Image shapes are different: {img.shape}, {img2.shape}.')
+    if input_order not in ['HWC', 'CHW']:
+        raise ValueError(f'Wrong input_order {input_order}. Supported input_orders are "HWC" and "CHW"')
+    if test_y_channel:
+        raise ValueError("calculate_delta_Eab: L*a*b* needs three colour channels; test_y_channel is not supported")
+    if img.dim() != 3 or img.shape[2 if input_order == 'HWC' else 0] != 3:
+        raise ValueError(f"calculate_delta_Eab: expected one image (h, w, 3) with 'HWC' or (3, h, w) with 'CHW', got {tuple(img.shape)} with {input_order!r}")
+    out = K.lab_metrics(img[None], img2[None], "hwc" if input_order == 'HWC' else "chw", crop_border)
+    h, w = (img.shape[0], img.shape[1]) if input_order == 'HWC' else (img.shape[1], img.shape[2])
+    return out[0, 0, 8] / ((h - 2 * int(crop_border)) * (w - 2 * int(crop_border)))
+
+
+def _drift_curves(sums, pixels, anchor_frames):
+    """sums float64 [F, 4] (tg_lab_metrics of one video) -> the curves of video_color_drift"""
+    mean = sums / pixels
+    lab, chroma = mean[:, :3], mean[:, 3]
+    drift = (lab - lab[:anchor_frames].mean(0, keepdim=True)).pow(2).sum(-1).sqrt()
+    return {"lab_mean": lab, "chroma": chroma, "drift": drift, "drift_mean": drift.mean(), "drift_max": drift.max(), "chroma_ratio": chroma[-1] / chroma[0]}
+
+
+def _check_anchor_frames(anchor_frames, who):
+    if not isinstance(anchor_frames, int) or isinstance(anchor_frames, bool) or anchor_frames < 1:
+        raise ValueError(f"{who}: anchor_frames must be a positive integer, got {anchor_frames!r}")
+
+
+def _one_video(frames, who):
+    if not isinstance(frames, torch.Tensor) or frames.dim() != 4:
+        raise ValueError(f"{who}: one video, uint8 [F, H, W, 3] or fp32 / bf16 (n, 3, h, w) in [0, 1], got {tuple(getattr(frames, 'shape', ()))}")
+
+
+def video_color_drift(frames, anchor_frames=1):
+    """How far the colour of ONE video wanders from its opening, from one tg_lab_metrics call.  frames: uint8 [F, H, W, 3], or fp32 / bf16 (n, 3, h, w) in [0, 1].
+    Returns float64 device tensors: "lab_mean" [F, 3], each frame's mean L*, a*, b*; "chroma" [F], its mean C*ab = sqrt(a^2 + b^2) over the pixels; "drift" [F], the
+    CIE76 distance between frame i's mean Lab and the mean of the first `anchor_frames` frames' means; 0-dim "drift_mean", "drift_max" and "chroma_ratio" = chroma of
+    the last frame over that of the first (a video that washes out falls below 1; NaN for a grey first frame).  Exposure and white-balance drift move lab_mean,
+    saturation drift moves chroma; unlike VideoConsistency's `first` curve neither reacts to what the frames show, only to their colour.  Nothing here waits for
+    the device."""
+    _one_video(frames, "video_color_drift")
+    _check_anchor_frames(anchor_frames, "video_color_drift")
+    if frames.shape[0] < anchor_frames:
+        raise ValueError(f"video_color_drift: {frames.shape[0]} frame(s) hold no {anchor_frames} anchor frames")
+    return _drift_curves(K.lab_metrics(frames, None, _layout(frames))[0], _lab_hw(frames, 0), anchor_frames)
+
+
+class VideoColorDrift:
+    """Streaming video_color_drift for long videos that arrive clip by clip.  `update(frames)` continues the current video with a clip (what video_color_drift
+    takes, F >= 1) and keeps its per-frame Lab sums on the device; `new_video()` closes the current video; `finalize()` closes it too and returns "videos" (an
+    int), per curve "lab_mean", "chroma", "drift" a list with one tensor per video, "drift_mean", "drift_max", "chroma_ratio" float64 [videos], and the pooled
+    0-dim "drift_mean_pooled" / "drift_max_pooled" / "chroma_ratio_pooled", their means over the videos.  A frame's sums come from that frame alone: a video fed in
+    pieces gives the bits of the video fed whole.  Nothing waits for the device before `finalize` returns its device tensors."""
+
+    def __init__(self, anchor_frames=1):
+        _check_anchor_frames(anchor_frames, "VideoColorDrift")
+        self.anchor_frames = anchor_frames
+        self._videos, self._open = [], None
+
+    def update(self, frames):
+        _one_video(frames, "VideoColorDrift.update")
+        sums = K.lab_metrics(frames, None, _layout(frames))[0]
+        if self._open is None:
+            self._open = {"sums": [], "pixels": _lab_hw(frames, 0)}
+        elif self._open["pixels"] != _lab_hw(frames, 0):
+            raise ValueError("VideoColorDrift.update: this clip's frames differ in size from the video's")
+        self._open["sums"].append(sums)
+        return sums / self._open["pixels"]
+
+    def new_video(self):
+        st = self._open
+        if st is None:
+            return
+        if sum(s.shape[0] for s in st["sums"]) < self.anchor_frames:
+            raise ValueError(f"VideoColorDrift: the current video has fewer than the {self.anchor_frames} anchor frames")
+        self._videos.append(_drift_curves(torch.cat(st["sums"]), st["pixels"], self.anchor_frames))
+        self._open = None
+
+    def finalize(self):
+        self.new_video()
+        if not self._videos:
+            raise RuntimeError("VideoColorDrift.finalize: no update yet")
+        out = {"videos": len(self._videos)}
+        for k in ("lab_mean", "chroma", "drift"):
+            out[k] = [v[k] for v in self._videos]
+        for k in ("drift_mean", "drift_max", "chroma_ratio"):
+            out[k] = torch.stack([v[k] for v in self._videos])
+            out[f"{k}_pooled"] = out[k].mean()
         return out

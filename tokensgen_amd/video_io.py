@@ -189,7 +189,14 @@ class VideoProcessor:
 
     frame_rate_factor n > 1 (2 .. 8; not in diffusers) raises the frame rate of the byte outputs by motion-compensated interpolation on the device
     (tokensgen_amd.motion.interpolate_frames with `block`, `radius`, `bidirectional`): T frames become (T - 1) n + 1, the originals unchanged at
-    every n-th place, and the caller writes them at `fps = output_fps * n`.  With the default, 1, every output is what it was and the motion code is never imported."""
+    every n-th place, and the caller writes them at `fps = output_fps * n`.  With the default, 1, every output is what it was and the motion code is never imported.
+
+    `set_color_match("meanstd" | "histogram", anchor=None, anchor_frames=8, strength=1.0, window=1)` (not in diffusers; the constructor's parameter list stays what it
+    was) makes the byte outputs colour-matched to an anchor on the device, before the interpolation, whose motion search assumes constant brightness
+    (tokensgen_amd.color.match_colors); it returns the processor, so `VideoProcessor(frame_rate_factor=2).set_color_match("meanstd")` reads in one line.
+    Without it (`color_match` is None) every output is what it was and the colour code is never imported."""
+
+    color_match, color_anchor, color_anchor_frames, color_strength, color_window = None, None, 8, 1.0, 1
 
     def __init__(self, frame_rate_factor=1, block=16, radius=16, bidirectional=True):
         if not isinstance(frame_rate_factor, int) or isinstance(frame_rate_factor, bool) or not 1 <= frame_rate_factor <= 8:
@@ -199,7 +206,21 @@ class VideoProcessor:
             from . import motion
             motion.check_block(block, radius, block, block, "VideoProcessor")
 
+    def set_color_match(self, mode, anchor=None, anchor_frames=8, strength=1.0, window=1):
+        """Colour-match the "uint8" and "pil" outputs (mode "meanstd" or "histogram"; None switches it off again).  anchor: None (each video's own first
+        anchor_frames frames), uint8 frames of any size, or an int64 [3, 256] histogram.  Every argument is checked here, before any kernel call.  Returns self."""
+        if mode is not None:
+            from . import color
+            color.check_params(mode, strength, window, 4.0, "VideoProcessor.set_color_match")
+            color.check_anchor_frames(anchor_frames, "VideoProcessor.set_color_match")
+            color.check_anchor(anchor, "VideoProcessor.set_color_match")
+        self.color_match, self.color_anchor, self.color_anchor_frames, self.color_strength, self.color_window = mode, anchor, anchor_frames, strength, window
+        return self
+
     def _upsample(self, frames_u8):
+        if self.color_match is not None:
+            from .color import match_colors
+            frames_u8 = match_colors(frames_u8, self.color_anchor, self.color_anchor_frames, self.color_match, self.color_strength, self.color_window)
         if self.frame_rate_factor == 1:
             return frames_u8
         from .motion import interpolate_frames
@@ -208,7 +229,10 @@ class VideoProcessor:
     def postprocess_video(self, video, output_type="np"):
         """video bf16 [B, 3, T, H, W] in [-1, 1].  "pt": [B, T, 3, H, W] in the input dtype, in [0, 1]; "np": float32 numpy [B, T, H, W, 3] in [0, 1]; "pil": B lists of T
         PIL images (rounded half to even); "uint8": uint8 tensor [B, T, H, W, 3] on the device, truncated: `(np_output * 255).astype(uint8)` byte for byte.
-        With frame_rate_factor > 1 "uint8" is interpolated, "pil" is interpolated from its rounded bytes, and the float outputs are refused."""
+        With frame_rate_factor > 1 "uint8" is interpolated, "pil" is interpolated from its rounded bytes, and the float outputs are refused; with color_match the
+        bytes are colour-matched first, and the float outputs are refused as well."""
+        if output_type in ("pt", "np") and self.color_match is not None:
+            raise ValueError(f"color_match {self.color_match!r} maps bytes: ask for output_type \"uint8\" (or \"pil\"), not {output_type!r}")
         if output_type in ("pt", "np") and self.frame_rate_factor > 1:
             raise ValueError(f"frame_rate_factor {self.frame_rate_factor} interpolates bytes: ask for output_type \"uint8\" (or \"pil\"), not {output_type!r}")
         if output_type == "pt":
