@@ -943,6 +943,40 @@ long tg_lab_metrics_ws_doubles(long frames, int h, int w, int two);
 int tg_lab_metrics(const void* a, long a_so, long a_si, long a_sc, long a_sr, long a_sp, const void* b, long b_so, long b_si, long b_sc, long b_sr, long b_sp,
                    int dtype, int n_outer, int n_inner, int h, int w, double* ws, double* out, hipStream_t stream);
 
+/* Baseline JPEG of the byte output (csrc/jpeg.hip; host side: tokensgen_amd/jpeg.py, which also writes the Motion-JPEG AVI).  Integer arithmetic with
+ * one exact definition, restated by tests/jpeg_ref.py: every frame is one exact byte string.
+ * Input: contiguous uint8 RGB [F][H][W][3], 1 <= H, W <= 65535.  subsampling is the integer 420 (MCU 16 x 16: Y Y Y Y Cb Cr, the four Y blocks in raster order) or 444
+ *   (MCU 8 x 8: Y Cb Cr); quality 1 .. 100; restart_interval r MCUs, 1 .. 65535.  MCUs in raster order; the frame is extended to whole MCUs by repeating its last
+ *   column and last row.
+ * Colour (libjpeg's fixed point, full range, arithmetic shifts): Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) +
+ *   32767) >> 16, Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16.  At 4:2:0 a chroma sample is (a + b + c + d + 2) >> 2 of the 2 x 2 converted samples.
+ * Forward DCT, two integer matrix products: A[u][x] = rint(8192 / 2 c_u cos((2 x + 1) u pi / 16)), c_0 = 1 / sqrt 2, otherwise 1; p = sample - 128;
+ *   t[y][u] = (sum_x A[u][x] p[y][x] + 512) >> 10; coef[v][u] = (sum_y A[v][y] t[y][u] + 32768) >> 16.  Everything fits in int32.
+ * Quantisation: the Annex K luminance and chrominance tables scaled by the IJG rule: s = 5000 / q for q < 50, otherwise 200 - 2 q; Q = clamp((base s + 50) / 100, 1,
+ *   255), integer division.  value = sign(c) ((|c| + Q / 2) / Q), integer division; AC values are clamped to +-1023.
+ * Entropy coding: baseline Huffman with the four Annex K tables.  DC prediction per component, 0 at the start of the scan and after every restart marker.  After every r
+ *   MCUs except the last group the remaining bits are filled with 1s to a byte and FF D0+(k mod 8) follows for the k-th marker (k from 0); the end of the scan is
+ *   filled the same way and FF D9 follows.  Every FF byte of entropy data is followed by 00.
+ * Frame: SOI; APP0 JFIF 1.01 (density unit 0, 1 : 1, no thumbnail); DQT 0, DQT 1 (own segments, 8-bit, zigzag order); SOF0 (precision 8, H, W, components 1, 2, 3,
+ *   sampling 22 11 11 or 11 11 11, tables 0, 1, 1); DHT DC0, AC0, DC1, AC1; DRI r; SOS (Ss 0, Se 63, Ah/Al 0); scan; EOI.  The header, SOI .. SOS, is
+ *   tg_jpeg_header_bytes() = 629 bytes for every frame.
+ * tg_jpeg_geometry(H, W, subsampling, r, what): 0 MCU rows, 1 MCU columns, 2 blocks per MCU, 3 restart segments per frame n_seg = ceil(MCUs / r), 4 int16
+ *   coefficients per frame; 0 for arguments the launches refuse.
+ * tg_jpeg_coeffs: coef (int16 [F][MCUs][blocks per MCU][64], 16-byte aligned) = the quantised coefficients in zigzag order.  One launch.
+ * tg_jpeg_segment_bytes: seg_bytes (int32 [F][n_seg]) = the bytes of every restart segment: its entropy data with stuffing and fill, and the two bytes of the marker
+ *   that ends it (FF D9 for a frame's last segment).  One launch, one lane per segment, no communication between segments.
+ * tg_jpeg_write: header and segments of every frame into data (uint8, data_bytes long): frame f's header at frame_offsets[f] (int64 [F]), segment s of frame f at
+ *   seg_offsets[f][s] (int64 [F][n_seg]; the caller's prefix sums: frame_offsets[f] + 629 + the bytes of the frame's earlier segments).  Two launches.  Writers
+ *   never share a byte: no atomics, bitwise reproducible, a frame's bytes depend on that frame alone.  Every store is checked against data and data + data_bytes:
+ *   offsets that do not fit lose bytes, they never store outside the buffer.
+ * None of the three allocates, copies or waits; the one wait of an encode is the caller's read of the total size between tg_jpeg_segment_bytes and tg_jpeg_write. */
+long tg_jpeg_header_bytes(void);
+long tg_jpeg_geometry(int H, int W, int subsampling, int restart_interval, int what);
+int tg_jpeg_coeffs(const void* frames, int F, int H, int W, int subsampling, int quality, void* coef, hipStream_t stream);
+int tg_jpeg_segment_bytes(const void* coef, int F, int H, int W, int subsampling, int restart_interval, void* seg_bytes, hipStream_t stream);
+int tg_jpeg_write(const void* coef, int F, int H, int W, int subsampling, int quality, int restart_interval, const void* seg_offsets, const void* frame_offsets,
+                  void* data, long data_bytes, hipStream_t stream);
+
 /* Dispatch overrides for the cross-check tests — NOT part of the operator surface.  The library reads no environment variable and keeps no other
  * process-wide state: the defaults are the shipped path, and these knobs only choose between two PRODUCT kernels of the same operator (each pair is held
  * bitwise or to rounding against each other by tests/).  Knobs: TG_ATTN_PP_MIN_WG (1024: workgroups from which the 8-wave attention kernel is used),

@@ -1428,3 +1428,53 @@ def lab_metrics(a, b, layout, crop_border=0):
     pb = None if b is None else b.data_ptr() + cb * (sb[3] + sb[4]) * b.element_size()
     L.check(_launch("lab_metrics", lib.tg_lab_metrics, pa, *sa, pb, *sb, _IMAGE_DTYPES[a.dtype], n_outer, n_inner, h, w, _p(ws), _p(out), _stream()), "tg_lab_metrics")
     return out
+
+
+JPEG_SUBSAMPLINGS = {"420": 420, "444": 444}
+
+
+def jpeg_geometry(H, W, subsampling, restart_interval=1):
+    """tg_jpeg_geometry: (MCU rows, MCU columns, blocks per MCU, restart segments per frame) of an H x W frame; refused arguments raise."""
+    lib = L.load()
+    g = tuple(lib.tg_jpeg_geometry(H, W, JPEG_SUBSAMPLINGS.get(subsampling, 0), restart_interval, what) for what in range(4))
+    if not all(g):
+        raise ValueError(f"jpeg: a frame of {H} x {W} (1..65535), subsampling {subsampling!r} ({sorted(JPEG_SUBSAMPLINGS)}), restart_interval {restart_interval!r} (1..65535)")
+    return g
+
+
+def jpeg_coeffs(frames, quality, subsampling):
+    """tg_jpeg_coeffs: contiguous uint8 [F, H, W, 3] -> int16 [F, MCUs, blocks per MCU, 64], the quantised DCT coefficients in zigzag order (the header's definition)."""
+    F, H, W = _chk_u8_frames(frames, "jpeg_coeffs")
+    rows, cols, bpm, _ = jpeg_geometry(H, W, subsampling)
+    coef = torch.empty(F, rows * cols, bpm, 64, dtype=torch.int16, device=frames.device)
+    L.check(_launch("jpeg_coeffs", L.load().tg_jpeg_coeffs, _p(frames), F, H, W, JPEG_SUBSAMPLINGS[subsampling], int(quality), _p(coef), _stream()), "tg_jpeg_coeffs")
+    return coef
+
+
+def _chk_jpeg_coef(coef, H, W, subsampling, restart_interval, who):
+    _chk(coef, "coef", torch.int16)
+    rows, cols, bpm, n_seg = jpeg_geometry(H, W, subsampling, restart_interval)
+    if coef.dim() != 4 or tuple(coef.shape[1:]) != (rows * cols, bpm, 64) or coef.shape[0] < 1 or not coef.is_contiguous():
+        raise ValueError(f"{who}: coef must be contiguous [F, {rows * cols}, {bpm}, 64], got {tuple(coef.shape)}")
+    return coef.shape[0], n_seg
+
+
+def jpeg_segment_bytes(coef, H, W, subsampling, restart_interval):
+    """tg_jpeg_segment_bytes: int32 [F, n_seg], the bytes of every restart segment with stuffing, fill and the marker that ends it (FF D9 for the last)."""
+    F, n_seg = _chk_jpeg_coef(coef, H, W, subsampling, restart_interval, "jpeg_segment_bytes")
+    out = torch.empty(F, n_seg, dtype=torch.int32, device=coef.device)
+    L.check(_launch("jpeg_segment_bytes", L.load().tg_jpeg_segment_bytes, _p(coef), F, H, W, JPEG_SUBSAMPLINGS[subsampling], int(restart_interval), _p(out), _stream()),
+            "tg_jpeg_segment_bytes")
+    return out
+
+
+def jpeg_write(coef, H, W, quality, subsampling, restart_interval, seg_offsets, frame_offsets, data):
+    """tg_jpeg_write: the header and the segments of every frame into `data` (uint8 [n]) at frame_offsets (int64 [F]) and seg_offsets (int64 [F, n_seg])."""
+    F, n_seg = _chk_jpeg_coef(coef, H, W, subsampling, restart_interval, "jpeg_write")
+    _chk(seg_offsets, "seg_offsets", torch.int64); _chk(frame_offsets, "frame_offsets", torch.int64); _chk(data, "data", torch.uint8)
+    if tuple(seg_offsets.shape) != (F, n_seg) or not seg_offsets.is_contiguous() or tuple(frame_offsets.shape) != (F,) or data.dim() != 1:
+        raise ValueError(f"jpeg_write: seg_offsets contiguous [{F}, {n_seg}], frame_offsets [{F}], data [n]; got {tuple(seg_offsets.shape)}, {tuple(frame_offsets.shape)}, "
+                         f"{tuple(data.shape)}")
+    L.check(_launch("jpeg_write", L.load().tg_jpeg_write, _p(coef), F, H, W, JPEG_SUBSAMPLINGS[subsampling], int(quality), int(restart_interval), _p(seg_offsets),
+                    _p(frame_offsets), _p(data), data.numel(), _stream()), "tg_jpeg_write")
+    return data

@@ -103,6 +103,9 @@ PROTOTYPES = {
     "tg_color_match_lut": [_vp, _i, _vp, _i, _vp, _i, _d, _i, _d, _vp, _vp, _vp],
     "tg_color_apply_lut": [_vp, _vp, _i, _i, _i, _vp, _vp],
     "tg_lab_metrics": [_vp, _l, _l, _l, _l, _l, _vp, _l, _l, _l, _l, _l, _i, _i, _i, _i, _i, _vp, _vp, _vp],
+    "tg_jpeg_coeffs": [_vp, _i, _i, _i, _i, _i, _vp, _vp],
+    "tg_jpeg_segment_bytes": [_vp, _i, _i, _i, _i, _i, _vp, _vp],
+    "tg_jpeg_write": [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _l, _vp],
     "tg_conv3d_cl": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _l, _i, _i, _i, _vp, _vp, _vp, _vp],
     "tg_conv3d_up2_subpixel": [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _l, _i, _vp, _vp, _vp],
     "tg_groupnorm_finalize": [_vp, _l, _i, _f, _vp, _vp],
@@ -149,6 +152,8 @@ QUERIES = {
     "tg_color_strip_bytes": [C.c_int],
     "tg_lab_metrics_tile": [C.c_int],
     "tg_lab_metrics_ws_doubles": [C.c_long, C.c_int, C.c_int, C.c_int],
+    "tg_jpeg_header_bytes": [],
+    "tg_jpeg_geometry": [C.c_int] * 5,
 }
 
 TG_BWD_ONE_KERNEL = 1

@@ -246,3 +246,11 @@ class VideoProcessor:
             by = self._upsample(K.video_to_uint8(video, 1, K.VIDEO_U8, 1)).cpu().numpy()
             return [[Image.fromarray(frame) for frame in clip] for clip in by]
         raise ValueError(f"output_type must be one of 'pt', 'np', 'pil', 'uint8'; got {output_type!r}")
+
+
+def export_to_video(video_frames, output_video_path, fps=8, quality=90):
+    """The last step of the reference's entry script (diffusers.utils.export_to_video, same argument order): the "uint8" output of `postprocess_video`, uint8
+    [T, H, W, 3] or [1, T, H, W, 3] on the device, as a Motion-JPEG .avi file (tokensgen_amd.jpeg, encoded on the device).  quality is the JPEG
+    quality, 1 .. 100.  Any other suffix is refused: there is no H.264 / mp4 encoder here.  Returns the path.  The JPEG code is imported by the first call."""
+    from . import jpeg
+    return jpeg.export_to_video(video_frames, output_video_path, fps, quality)
