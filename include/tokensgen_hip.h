@@ -977,6 +977,57 @@ int tg_jpeg_segment_bytes(const void* coef, int F, int H, int W, int subsampling
 int tg_jpeg_write(const void* coef, int F, int H, int W, int subsampling, int quality, int restart_interval, const void* seg_offsets, const void* frame_offsets,
                   void* data, long data_bytes, hipStream_t stream);
 
+/* Baseline JPEG decoding, the inverse of the above (csrc/jpeg_decode.hip, csrc/jpeg_entropy_dec.h; host side: tokensgen_amd/jpeg.py, which parses the headers and reads
+ * the Motion-JPEG AVI).  Integer arithmetic with one exact definition, restated by tests/jpeg_dec_ref.py: a decoded frame is one exact byte array.
+ * Accepted: baseline sequential DCT (SOF0), 8-bit precision, three components read as Y Cb Cr (the first of SOF0 is Y, ids are free), sampling (2x2, 1x1, 1x1) = 420 or
+ *   all 1x1 = 444, one interleaved scan (Ss 0, Se 63, Ah = Al = 0), 8-bit DQT in any of four slots, any DHT (a frame with none uses the four Annex K tables, the AVI
+ *   MJPG convention), DRI absent, 0 or any interval r.  The host resolves the tables per component; the device sees byte ranges and tables only.
+ * Entropy decoding: canonical Huffman per Annex F.  DC prediction per component, 0 at the start of the scan and after every restart marker; FF 00 un-stuffs to FF; an
+ *   FF followed by anything else ends a segment's data.  Restart segment s holds MCUs [s r, min((s + 1) r, MCUs)).  An AC symbol (run, size): size 0 with run 0 ends the
+ *   block, with run 15 skips 16 coefficients, any other run is an invalid code; otherwise the index moves on by run and must stay <= 63.  The result is the quantised
+ *   coefficients in zigzag order, int16 [F][MCUs][blocks per MCU][64], the layout of tg_jpeg_coeffs; the running DC is kept in int32 and stored clamped to int16.
+ * Reconstruction, with the table A[u][x] of the forward transform: d[v][u] = clamp(coef Q, -2048, 2047); t[v][x] = (sum_u A[u][x] d[v][u] + 512) >> 10;
+ *   p[y][x] = (sum_v A[v][y] t[v][x] + 32768) >> 16; sample = clamp(p + 128, 0, 255).  sum_u |A[u][x]| <= 31015: the first sum stays below 6.4e7, the second below
+ *   1.93e9, both inside int32.
+ * Chroma at 420: libjpeg's triangle filter on the REAL chroma plane of ceil(H / 2) x ceil(W / 2) samples (not the MCU padding); a neighbour outside it is the edge
+ *   sample.  Vertically s = 3 near + far, far the row above for even output rows and the row below for odd ones; horizontally out[2 i] = (3 s[i] + s[i - 1] + 8) >> 4,
+ *   out[2 i + 1] = (3 s[i] + s[i + 1] + 7) >> 4.
+ * Colour (libjpeg's fixed point, cb and cr minus 128, arithmetic shifts): R = Y + ((91881 cr + 32768) >> 16), G = Y + ((-22554 cb - 46802 cr + 32768) >> 16),
+ *   B = Y + ((116130 cb + 32768) >> 16), each clamped to 0 .. 255.  Output uint8 [F][H][W][3], cropped to H x W.
+ * status (int32 [F]) collects, per frame, TG_JPEG_ST_INVALID_CODE (no Huffman code matches, or an AC symbol baseline does not have), _COEF_INDEX (a run past
+ *   coefficient 63), _CATEGORY (a DC category above 11 or an AC size above 10), _OUT_OF_BITS (a segment ends before its MCUs), _RST_COUNT (the scan does not hold
+ *   n_seg - 1 restart markers), _RST_NUMBER (a marker that is not FF D0 + (k mod 8)), _RANGE (a byte range or table index outside its buffer).  After an error the
+ *   block and every later block of that restart segment are zero; other segments and frames are not touched by it.
+ * tg_jpeg_huff_table (host only, no device call): BITS [16] and HUFFVAL [n_vals] -> one table of tg_jpeg_huff_table_bytes() = 912 bytes (maxcode, valptr - mincode, an
+ *   8-bit look-ahead, the values); refuses counts that do not add up and over-subscribed codes.  A table set is six of them: component c's DC at 2 c, AC at 2 c + 1.
+ * tg_jpeg_decode_segments(H, W, subsampling, r): n_seg = ceil(MCUs / r), 1 for r = 0; 0 for refused arguments.
+ * tg_jpeg_find_segments: scan_begin / scan_end (int64 [F]): the bytes of every frame's entropy data in data, as the host parsed them.  seg_begin / seg_end (int64
+ *   [F][n_seg]) = the bytes of every restart segment without its marker, found and compacted in order on the device; STORES status[f] (0 or _RST_COUNT, _RST_NUMBER,
+ *   _RANGE), so it runs first.  One launch, one workgroup per frame.
+ * tg_jpeg_decode_coeffs: one lane per restart segment; htabs: n_sets table sets, htab_index (int32 [F]) the set of every frame.  Writes every coefficient of every MCU,
+ *   zeros included; ORs errors into status[f].  The bit reader reads inside [seg_begin, seg_end) and inside [0, data_bytes) only; a lane does at most 64 symbol steps
+ *   per block.  One launch.
+ * tg_jpeg_idct_rgb: qtabs uint16 [n_qsets][3][64] in natural order per component, qtab_index (int32 [F]); ws: tg_jpeg_idct_ws_bytes(F, H, W, subsampling) bytes,
+ *   16-byte aligned, receives the three sample planes padded to whole MCUs; rgb: the output, rgb_bytes long: every store is checked against its end.  Two launches.
+ * None of them allocates, copies or waits; the one wait of a decode is the caller's read of status. */
+#define TG_JPEG_ST_INVALID_CODE 1
+#define TG_JPEG_ST_COEF_INDEX 2
+#define TG_JPEG_ST_CATEGORY 4
+#define TG_JPEG_ST_OUT_OF_BITS 8
+#define TG_JPEG_ST_RST_COUNT 16
+#define TG_JPEG_ST_RST_NUMBER 32
+#define TG_JPEG_ST_RANGE 64
+long tg_jpeg_huff_table_bytes(void);
+int tg_jpeg_huff_table(const void* bits, const void* vals, int n_vals, void* table);
+long tg_jpeg_decode_segments(int H, int W, int subsampling, int restart_interval);
+int tg_jpeg_find_segments(const void* data, long data_bytes, const void* scan_begin, const void* scan_end, int F, long n_seg, void* seg_begin, void* seg_end,
+                          void* status, hipStream_t stream);
+int tg_jpeg_decode_coeffs(const void* data, long data_bytes, const void* seg_begin, const void* seg_end, int F, int H, int W, int subsampling, int restart_interval,
+                          const void* htabs, int n_sets, const void* htab_index, void* coef, void* status, hipStream_t stream);
+long tg_jpeg_idct_ws_bytes(int F, int H, int W, int subsampling);
+int tg_jpeg_idct_rgb(const void* coef, int F, int H, int W, int subsampling, const void* qtabs, int n_qsets, const void* qtab_index, void* ws, long ws_bytes, void* rgb,
+                     long rgb_bytes, hipStream_t stream);
+
 /* Dispatch overrides for the cross-check tests — NOT part of the operator surface.  The library reads no environment variable and keeps no other
  * process-wide state: the defaults are the shipped path, and these knobs only choose between two PRODUCT kernels of the same operator (each pair is held
  * bitwise or to rounding against each other by tests/).  Knobs: TG_ATTN_PP_MIN_WG (1024: workgroups from which the 8-wave attention kernel is used),

@@ -1478,3 +1478,92 @@ def jpeg_write(coef, H, W, quality, subsampling, restart_interval, seg_offsets, 
     L.check(_launch("jpeg_write", L.load().tg_jpeg_write, _p(coef), F, H, W, JPEG_SUBSAMPLINGS[subsampling], int(quality), int(restart_interval), _p(seg_offsets),
                     _p(frame_offsets), _p(data), data.numel(), _stream()), "tg_jpeg_write")
     return data
+
+
+# the bits of the decoder's status (TG_JPEG_ST_* of the header) and what each says
+JPEG_STATUS = {1: "an invalid Huffman code", 2: "a coefficient index past 63", 4: "a DC category above 11 or an AC size above 10", 8: "a restart segment runs out of bits",
+               16: "the count of restart markers is not that of the restart interval", 32: "a restart marker out of order", 64: "a byte range or table index outside its buffer"}
+
+
+def jpeg_huff_table(bits, vals):
+    """tg_jpeg_huff_table (host only): BITS (16 counts) and HUFFVAL -> the 912 bytes of one decoding table; ValueError for counts that do not add up or an
+    over-subscribed code."""
+    lib = L.load()
+    bits, vals = bytes(bits), bytes(vals)
+    if len(bits) != 16:
+        raise ValueError(f"jpeg_huff_table: BITS has 16 counts, got {len(bits)}")
+    out = (C.c_uint32 * (lib.tg_jpeg_huff_table_bytes() // 4))()
+    if lib.tg_jpeg_huff_table(bits, vals, len(vals), C.addressof(out)) != 0:
+        raise ValueError(lib.tg_last_error_string().decode())
+    return bytes(out)
+
+
+def jpeg_decode_segments(H, W, subsampling, restart_interval):
+    """tg_jpeg_decode_segments: restart segments per frame, 1 for restart_interval 0 (no markers); refused arguments raise."""
+    n = L.load().tg_jpeg_decode_segments(H, W, JPEG_SUBSAMPLINGS.get(subsampling, 0), restart_interval)
+    if not n:
+        raise ValueError(f"jpeg: a frame of {H} x {W} (1..65535), subsampling {subsampling!r} ({sorted(JPEG_SUBSAMPLINGS)}), restart_interval {restart_interval!r} (0..65535)")
+    return n
+
+
+def _chk_vec(t, name, dtype, shape):
+    _chk(t, name, dtype)
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{name}: expected contiguous {list(shape)}, got {tuple(t.shape)}")
+
+
+def jpeg_find_segments(data, scan_begin, scan_end, n_seg, status):
+    """tg_jpeg_find_segments: data uint8 [n], scan_begin / scan_end int64 [F] -> (seg_begin, seg_end) int64 [F, n_seg], the bytes of every restart segment; stores
+    status (int32 [F])."""
+    _chk(data, "data", torch.uint8)
+    F = scan_begin.numel() if isinstance(scan_begin, torch.Tensor) else 0
+    if data.dim() != 1 or data.numel() < 1 or not data.is_contiguous() or F < 1 or int(n_seg) < 1:
+        raise ValueError(f"jpeg_find_segments: data uint8 [n >= 1], at least one frame and one segment; got {tuple(data.shape)}, F={F}, n_seg={n_seg}")
+    _chk_vec(scan_begin, "scan_begin", torch.int64, (F,)); _chk_vec(scan_end, "scan_end", torch.int64, (F,)); _chk_vec(status, "status", torch.int32, (F,))
+    seg_begin = torch.empty(F, int(n_seg), dtype=torch.int64, device=data.device)
+    seg_end = torch.empty_like(seg_begin)
+    L.check(_launch("jpeg_find_segments", L.load().tg_jpeg_find_segments, _p(data), data.numel(), _p(scan_begin), _p(scan_end), F, int(n_seg), _p(seg_begin), _p(seg_end),
+                    _p(status), _stream()), "tg_jpeg_find_segments")
+    return seg_begin, seg_end
+
+
+def jpeg_decode_coeffs(data, seg_begin, seg_end, H, W, subsampling, restart_interval, htabs, htab_index, status):
+    """tg_jpeg_decode_coeffs: -> int16 [F, MCUs, blocks per MCU, 64], every coefficient written; htabs uint8 [sets, 6 * 912], htab_index int32 [F]; ORs into status."""
+    _chk(data, "data", torch.uint8)
+    n_seg = jpeg_decode_segments(H, W, subsampling, restart_interval)
+    rows, cols, bpm, _ = jpeg_geometry(H, W, subsampling)
+    _chk(seg_begin, "seg_begin", torch.int64)
+    F = seg_begin.shape[0] if seg_begin.dim() == 2 else 0
+    if data.dim() != 1 or data.numel() < 1 or not data.is_contiguous() or F < 1:
+        raise ValueError(f"jpeg_decode_coeffs: data uint8 [n >= 1], seg_begin [F, {n_seg}]; got {tuple(data.shape)}, {tuple(seg_begin.shape)}")
+    _chk_vec(seg_begin, "seg_begin", torch.int64, (F, n_seg)); _chk_vec(seg_end, "seg_end", torch.int64, (F, n_seg))
+    _chk_vec(htab_index, "htab_index", torch.int32, (F,)); _chk_vec(status, "status", torch.int32, (F,))
+    _chk(htabs, "htabs", torch.uint8)
+    set_bytes = 6 * L.load().tg_jpeg_huff_table_bytes()
+    if htabs.dim() != 2 or htabs.shape[0] < 1 or htabs.shape[1] != set_bytes or not htabs.is_contiguous():
+        raise ValueError(f"jpeg_decode_coeffs: htabs must be contiguous uint8 [sets, {set_bytes}], got {tuple(htabs.shape)}")
+    coef = torch.empty(F, rows * cols, bpm, 64, dtype=torch.int16, device=data.device)
+    L.check(_launch("jpeg_decode_coeffs", L.load().tg_jpeg_decode_coeffs, _p(data), data.numel(), _p(seg_begin), _p(seg_end), F, H, W, JPEG_SUBSAMPLINGS[subsampling],
+                    int(restart_interval), _p(htabs), htabs.shape[0], _p(htab_index), _p(coef), _p(status), _stream()), "tg_jpeg_decode_coeffs")
+    return coef
+
+
+def jpeg_idct_rgb(coef, H, W, subsampling, qtabs, qtab_index, out=None):
+    """tg_jpeg_idct_rgb: coef int16 [F, MCUs, blocks per MCU, 64], qtabs uint16 [sets, 3, 64] (natural order), qtab_index int32 [F] -> uint8 [F, H, W, 3].  `out`: a
+    flat uint8 buffer to fill instead (every store is checked against its end)."""
+    F, _ = _chk_jpeg_coef(coef, H, W, subsampling, 1, "jpeg_idct_rgb")
+    _chk(qtabs, "qtabs", torch.uint16)
+    if qtabs.dim() != 3 or qtabs.shape[0] < 1 or tuple(qtabs.shape[1:]) != (3, 64) or not qtabs.is_contiguous():
+        raise ValueError(f"jpeg_idct_rgb: qtabs must be contiguous uint16 [sets, 3, 64], got {tuple(qtabs.shape)}")
+    _chk_vec(qtab_index, "qtab_index", torch.int32, (F,))
+    lib = L.load()
+    ws = torch.empty(lib.tg_jpeg_idct_ws_bytes(F, H, W, JPEG_SUBSAMPLINGS[subsampling]), dtype=torch.uint8, device=coef.device)
+    if out is None:
+        out = torch.empty(F, H, W, 3, dtype=torch.uint8, device=coef.device)
+    else:
+        _chk(out, "out", torch.uint8)
+        if out.dim() != 1 or out.numel() < 1:
+            raise ValueError(f"jpeg_idct_rgb: out must be a flat uint8 buffer, got {tuple(out.shape)}")
+    L.check(_launch("jpeg_idct_rgb", lib.tg_jpeg_idct_rgb, _p(coef), F, H, W, JPEG_SUBSAMPLINGS[subsampling], _p(qtabs), qtabs.shape[0], _p(qtab_index), _p(ws),
+                    ws.numel(), _p(out), out.numel(), _stream()), "tg_jpeg_idct_rgb")
+    return out

@@ -106,6 +106,10 @@ PROTOTYPES = {
     "tg_jpeg_coeffs": [_vp, _i, _i, _i, _i, _i, _vp, _vp],
     "tg_jpeg_segment_bytes": [_vp, _i, _i, _i, _i, _i, _vp, _vp],
     "tg_jpeg_write": [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _l, _vp],
+    "tg_jpeg_huff_table": [_vp, _vp, _i, _vp],
+    "tg_jpeg_find_segments": [_vp, _l, _vp, _vp, _i, _l, _vp, _vp, _vp, _vp],
+    "tg_jpeg_decode_coeffs": [_vp, _l, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp],
+    "tg_jpeg_idct_rgb": [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _l, _vp, _l, _vp],
     "tg_conv3d_cl": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _l, _i, _i, _i, _vp, _vp, _vp, _vp],
     "tg_conv3d_up2_subpixel": [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _l, _i, _vp, _vp, _vp],
     "tg_groupnorm_finalize": [_vp, _l, _i, _f, _vp, _vp],
@@ -154,6 +158,9 @@ QUERIES = {
     "tg_lab_metrics_ws_doubles": [C.c_long, C.c_int, C.c_int, C.c_int],
     "tg_jpeg_header_bytes": [],
     "tg_jpeg_geometry": [C.c_int] * 5,
+    "tg_jpeg_huff_table_bytes": [],
+    "tg_jpeg_decode_segments": [C.c_int] * 4,
+    "tg_jpeg_idct_ws_bytes": [C.c_int] * 4,
 }
 
 TG_BWD_ONE_KERNEL = 1

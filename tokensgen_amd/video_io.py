@@ -2,8 +2,9 @@
 
 Front end: the arithmetic of `load_video` (longvgen/data/long_video.py:28-76) after the container is decoded: frame index sampling (:37-51, `sample_frame_indices`),
 then `video / 255.` -> resize -> crop / pad -> `* 2 - 1` (:61-76) with `resize_for_rectangle_crop` (longvgen/data/utils.py:112-140, bicubic, centre crop) or
-`ResolutionControl.__call__` (utils.py:13-107, optional pad with -1, bilinear to exactly output_res), in one launch of tg_video_resample (csrc/video.hip).  Decoding the
-container stays outside (no decoder library here): `prepare_video` takes the uint8 [F, H, W, 3] frames a decoder delivers.
+`ResolutionControl.__call__` (utils.py:13-107, optional pad with -1, bilinear to exactly output_res), in one launch of tg_video_resample (csrc/video.hip).
+`prepare_video` takes the uint8 [F, H, W, 3] frames a decoder delivers; `load_video` is the whole function for Motion-JPEG .avi files, decoded on the device by
+tokensgen_amd.jpeg; there is no decoder library here, so every other container is refused by name.
 
 STATED ASSUMPTION: torchvision 0.19.1 `resize` defaults to antialias=True and, on a float tensor, is
 `F.interpolate(img, size, mode, align_corners=False, antialias=True)` without a clamp; torchvision's source is absent, so that call is taken as the definition and
@@ -246,6 +247,15 @@ class VideoProcessor:
             by = self._upsample(K.video_to_uint8(video, 1, K.VIDEO_U8, 1)).cpu().numpy()
             return [[Image.fromarray(frame) for frame in clip] for clip in by]
         raise ValueError(f"output_type must be one of 'pt', 'np', 'pil', 'uint8'; got {output_type!r}")
+
+
+def load_video(video_path, output_res, nf_per_chunk, pad_to_fit, sample_fps, start_t, end_t, max_num_chunks, crop_to_fit=False, device=None):
+    """The first step of the reference's entry script (`load_video`, long_video.py:28-76, same parameter order): a Motion-JPEG .avi file (one that `export_to_video`
+    wrote, or any baseline MJPG AVI) -> bf16 [1, F, 3, oh, ow] in [-1, 1] on the device.  The file's index is read on the host, `sample_frame_indices` picks the
+    frames, they are decoded on the device (tokensgen_amd.jpeg.MJPEGReader) and go through `prepare_video`.  Any other suffix is refused: there is no
+    H.264 / mp4 decoder here.  The JPEG code is imported by the first call."""
+    from . import jpeg
+    return jpeg.load_video(video_path, output_res, nf_per_chunk, pad_to_fit, sample_fps, start_t, end_t, max_num_chunks, crop_to_fit, device)
 
 
 def export_to_video(video_frames, output_video_path, fps=8, quality=90):
