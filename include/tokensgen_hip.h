@@ -1009,7 +1009,20 @@ int tg_jpeg_write(const void* coef, int F, int H, int W, int subsampling, int qu
  *   per block.  One launch.
  * tg_jpeg_idct_rgb: qtabs uint16 [n_qsets][3][64] in natural order per component, qtab_index (int32 [F]); ws: tg_jpeg_idct_ws_bytes(F, H, W, subsampling) bytes,
  *   16-byte aligned, receives the three sample planes padded to whole MCUs; rgb: the output, rgb_bytes long: every store is checked against its end.  Two launches.
- * None of them allocates, copies or waits; the one wait of a decode is the caller's read of status. */
+ * tg_jpeg_decode_coeffs_sync (csrc/jpeg_decode_sync.hip, csrc/jpeg_entropy_sync.h): the same coefficients, bit for bit, with parallel decoding INSIDE a
+ *   restart segment, for streams without restart markers or with long intervals.  Takes the ranges of tg_jpeg_find_segments.  A decoder state at a symbol boundary is
+ *   (bit position in the raw bytes, block within the MCU, zigzag index; index 0: a DC code is next).  A segment's bytes are cut into subsequences of sub_bytes (16, 32,
+ *   64, 128 or 256) raw bytes; lane i decodes from the first bit of subsequence i with the guess (block 0, index 0) while a symbol starts inside its subsequence, and in
+ *   rounds takes lane i - 1's exit as its entry, decoding again where that differs from the entry it used.  Lane 0's entry is true and truth moves on by one lane per
+ *   round: after at most lanes - 1 rounds every entry is the serial decoder's state.  A prefix sum of the blocks each lane started places its coefficients, a prefix
+ *   sum per component turns the DC differences into the running DC (int32, stored clamped to int16).  One workgroup of 1024 lanes per (segment, frame), a longer
+ *   segment 1024 subsequences at a time; every loop is bounded by sizes known before it starts, every store's block index is checked.  Writes every coefficient of every
+ *   MCU.  STORES clean[f] (int32 [F]) = 1 only if every segment of the frame converged with no invalid lane on the chain, started exactly its blocks, ended between two
+ *   MCUs and had a valid range and table index, else 0: the coefficients of a frame that is not clean are not a result, and the caller decodes it with
+ *   tg_jpeg_decode_coeffs.  STORES rounds[f] (int32 [F]), the most rounds (the first decode included) that 1024 subsequences of the frame took.  NEVER touches status:
+ *   lanes that start from a wrong guess meet errors all the time.  ws: tg_jpeg_sync_ws_bytes(F, H, W, subsampling, r) bytes (0 for refused arguments), 4-byte
+ *   aligned.  Two launches.
+ * None of them allocates, copies or waits; the one wait of a decode is the caller's read of status (and of clean). */
 #define TG_JPEG_ST_INVALID_CODE 1
 #define TG_JPEG_ST_COEF_INDEX 2
 #define TG_JPEG_ST_CATEGORY 4
@@ -1024,6 +1037,10 @@ int tg_jpeg_find_segments(const void* data, long data_bytes, const void* scan_be
                           void* status, hipStream_t stream);
 int tg_jpeg_decode_coeffs(const void* data, long data_bytes, const void* seg_begin, const void* seg_end, int F, int H, int W, int subsampling, int restart_interval,
                           const void* htabs, int n_sets, const void* htab_index, void* coef, void* status, hipStream_t stream);
+long tg_jpeg_sync_ws_bytes(int F, int H, int W, int subsampling, int restart_interval);
+int tg_jpeg_decode_coeffs_sync(const void* data, long data_bytes, const void* seg_begin, const void* seg_end, int F, int H, int W, int subsampling,
+                               int restart_interval, const void* htabs, int n_sets, const void* htab_index, int sub_bytes, void* ws, long ws_bytes, void* coef,
+                               void* clean, void* rounds, hipStream_t stream);
 long tg_jpeg_idct_ws_bytes(int F, int H, int W, int subsampling);
 int tg_jpeg_idct_rgb(const void* coef, int F, int H, int W, int subsampling, const void* qtabs, int n_qsets, const void* qtab_index, void* ws, long ws_bytes, void* rgb,
                      long rgb_bytes, hipStream_t stream);

@@ -15,7 +15,8 @@ parser in plain Python, and an AVI 1.0 reader around it; tests/jpeg_dec_ref.py r
     from tokensgen_amd.jpeg import parse_jpeg, decode_jpeg, load_jpeg, MJPEGReader, read_mjpeg_avi
 
 `parse_jpeg` holds every refusal (progressive, arithmetic coding, 12-bit, other sampling factors, ...), `decode_jpeg` turns a batch of streams into uint8 frames on the
-device with one copy up and one wait, `MJPEGReader` reads our own files and any other baseline Motion-JPEG AVI."""
+device with one copy up and one wait, `MJPEGReader` reads our own files and any other baseline Motion-JPEG AVI.  Streams without restart markers, what most
+encoders write, are decoded in parallel inside the frame (tg_jpeg_decode_coeffs_sync, csrc/jpeg_decode_sync.hip): `entropy_plan` says when."""
 import functools
 import os
 import re
@@ -434,13 +435,42 @@ class JpegDecodeError(ValueError):
     status = None
 
 
-def decode_jpeg(data, offsets=None, device=None):
+ENTROPY_MODES = ("auto", "segment", "sync")
+# Set from profiles/jpeg_sync_bench.json (tools/bench_jpeg_decode.py --sync, 49 frames of 480 x 720).  SYNC_MIN_MCUS: the fewest MCUs per restart segment, of the
+# intervals measured, from which tg_jpeg_decode_coeffs_sync beat one lane per segment on all four clips with the min - max ranges apart (at 90 it won on the two
+# 4:2:0 clips only, at 45 on none).  SYNC_SUB_BYTES: 128 was the fastest of 64 / 128 / 256 on both smooth clips without markers and within a third of the fastest (256) on noise.
+SYNC_MIN_MCUS = 270
+SYNC_SUB_BYTES = 128
+
+
+def entropy_plan(H, W, subsampling, restart_interval):
+    """Which entropy launch decode_jpeg(entropy="auto") uses for frames of this geometry: ("segment", None), one lane per restart segment (tg_jpeg_decode_coeffs), or
+    ("sync", sub_bytes), parallel decoding inside every segment (tg_jpeg_decode_coeffs_sync).  A pure function of the geometry, no device call.  "sync" where a
+    segment holds at least SYNC_MIN_MCUS MCUs; a frame that is one segment (no markers, or an interval of at least its MCUs) qualifies from two MCUs on: one MCU is too
+    small to cut.  restart_interval 0: no markers."""
+    if not _is_int(restart_interval) or not 0 <= restart_interval <= 65535:
+        raise ValueError(f"entropy_plan: restart_interval must be an integer in 0..65535, got {restart_interval!r}")
+    rows, cols, _, _ = K.jpeg_geometry(H, W, subsampling)
+    n_mcu = rows * cols
+    per_segment = n_mcu if restart_interval == 0 else min(restart_interval, n_mcu)
+    if per_segment >= SYNC_MIN_MCUS or (per_segment == n_mcu and n_mcu >= 2):
+        return ("sync", SYNC_SUB_BYTES)
+    return ("segment", None)
+
+
+def decode_jpeg(data, offsets=None, device=None, entropy="auto"):
     """Baseline JPEG frames -> uint8 [F, H, W, 3] on the device.  data: a list of `bytes` (one frame each), or a uint8 tensor holding all frames with `offsets` (int64
     [F + 1]) as encode_jpeg returns them; a device tensor is copied to the host once, for the header parsing, and decoded where it is.  All frames of a call share
     height, width, subsampling and restart interval (ValueError otherwise); their tables may differ.  The headers are parsed here (parse_jpeg), the bytes go up in one
     copy with the tables behind them, and after the launches the host reads status [F]: the one wait of a decode.  A non-zero entry raises JpegDecodeError (a
-    ValueError) naming the first bad frame and the condition.  One lane decodes one restart segment: a stream without restart markers decodes with one lane per frame."""
+    ValueError) naming the first bad frame and the condition.
+    entropy: "segment" decodes one lane per restart segment, so a stream without restart markers decodes with one lane per frame; "sync" decodes in parallel inside
+    every segment and reads status and the decoder's own verdict `clean` in the same one wait; "auto" (the default) follows entropy_plan.  The result
+    is the same byte array either way.  Where "sync" does not vouch for every frame (a damaged stream, or junk behind the last MCU that the serial decoder never
+    reads), the call is decoded again by "segment", and that run's frames, status and JpegDecodeError are the result: a second wait, on that path only."""
     who = "decode_jpeg"
+    if entropy not in ENTROPY_MODES:
+        raise ValueError(f"{who}: entropy must be one of {ENTROPY_MODES}, got {entropy!r}")
     chunks, on_device, o = _frames_of(data, offsets, who)
     F = len(chunks)
     infos = [parse_jpeg(c, i) for i, c in enumerate(chunks)]
@@ -477,8 +507,19 @@ def decode_jpeg(data, offsets=None, device=None):
     stream_dev = on_device.contiguous() if on_device is not None else up[:o[-1]]
     scan_begin, scan_end, htab_index, qtab_index = cut(0, torch.int64), cut(1, torch.int64), cut(2, torch.int32), cut(3, torch.int32)
     htabs, qtabs = cut(4, torch.uint8).view(len(hsets), -1), cut(5, torch.uint16).view(len(qsets), 3, 64)
-    status = torch.empty(F, dtype=torch.int32, device=dev)
     n_seg = K.jpeg_decode_segments(H, W, sub, ri)
+    mode, sub_bytes = entropy_plan(H, W, sub, ri) if entropy == "auto" else (entropy, SYNC_SUB_BYTES)
+    if mode == "sync":
+        flags = torch.empty(3 * F, dtype=torch.int32, device=dev)               # status, clean and rounds: one buffer, one read
+        status, clean, rounds = flags[:F], flags[F:2 * F], flags[2 * F:]
+        seg_begin, seg_end = K.jpeg_find_segments(stream_dev, scan_begin, scan_end, n_seg, status)
+        coef = K.jpeg_decode_coeffs_sync(stream_dev, seg_begin, seg_end, H, W, sub, ri, htabs, htab_index, sub_bytes, clean, rounds)
+        out = K.jpeg_idct_rgb(coef, H, W, sub, qtabs, qtab_index)
+        got = flags.cpu()                                                       # the one wait of the call
+        if not bool(got[:F].any()) and bool((got[F:2 * F] == 1).all()):
+            return out
+        # not vouched for: the serial decoder decides, and its status, frames and error text are the result
+    status = torch.empty(F, dtype=torch.int32, device=dev)
     seg_begin, seg_end = K.jpeg_find_segments(stream_dev, scan_begin, scan_end, n_seg, status)
     coef = K.jpeg_decode_coeffs(stream_dev, seg_begin, seg_end, H, W, sub, ri, htabs, htab_index, status)
     out = K.jpeg_idct_rgb(coef, H, W, sub, qtabs, qtab_index)
@@ -503,7 +544,7 @@ def _gpu(device, who):
 
 
 def load_jpeg(path, device=None):
-    """One baseline .jpg file -> uint8 [H, W, 3] on the device."""
+    """One baseline .jpg file -> uint8 [H, W, 3] on the device; a file without restart markers is decoded in parallel inside the frame (entropy_plan)."""
     with open(path, "rb") as fh:
         return decode_jpeg([fh.read()], device=device)[0]
 
@@ -514,7 +555,8 @@ def _avi_bad(path, what):
 
 class MJPEGReader:
     """A Motion-JPEG AVI 1.0 file (ours, or any baseline MJPG AVI): `.frames` / len(), `.size` (H, W), `.fps` (a Fraction, dwRate / dwScale), `get_avg_fps()`;
-    `get_batch(indices)` and `read(start=0, stop=None)` return uint8 [n, H, W, 3] on the device, decoded at most BATCH frames per decode_jpeg call; an index may repeat.
+    `get_batch(indices)` and `read(start=0, stop=None)` return uint8 [n, H, W, 3] on the device, decoded at most BATCH frames per decode_jpeg call (entropy "auto":
+    frames without restart markers are decoded in parallel inside the frame); an index may repeat.
     The first `strl` whose `strh` is `vids` with handler or biCompression MJPG is the stream; its NNdc / NNdb chunks are the frames, other streams' chunks are skipped,
     LIST 'rec ' is walked.  `idx1` is used when present (offsets relative to the 'movi' fourcc or to the file: whichever finds the chunk's fourcc), otherwise `movi` is
     walked.  A chunk of length 0 repeats the frame before it.  OpenDML (RIFF AVIX, indx) and other codecs are refused by name; a truncated file is a ValueError.  The

@@ -1527,24 +1527,54 @@ def jpeg_find_segments(data, scan_begin, scan_end, n_seg, status):
     return seg_begin, seg_end
 
 
-def jpeg_decode_coeffs(data, seg_begin, seg_end, H, W, subsampling, restart_interval, htabs, htab_index, status):
-    """tg_jpeg_decode_coeffs: -> int16 [F, MCUs, blocks per MCU, 64], every coefficient written; htabs uint8 [sets, 6 * 912], htab_index int32 [F]; ORs into status."""
+def _chk_jpeg_decode_args(who, data, seg_begin, seg_end, H, W, subsampling, restart_interval, htabs, htab_index):
+    """what tg_jpeg_decode_coeffs and tg_jpeg_decode_coeffs_sync both take -> (F, MCUs, blocks per MCU)"""
     _chk(data, "data", torch.uint8)
     n_seg = jpeg_decode_segments(H, W, subsampling, restart_interval)
     rows, cols, bpm, _ = jpeg_geometry(H, W, subsampling)
     _chk(seg_begin, "seg_begin", torch.int64)
     F = seg_begin.shape[0] if seg_begin.dim() == 2 else 0
     if data.dim() != 1 or data.numel() < 1 or not data.is_contiguous() or F < 1:
-        raise ValueError(f"jpeg_decode_coeffs: data uint8 [n >= 1], seg_begin [F, {n_seg}]; got {tuple(data.shape)}, {tuple(seg_begin.shape)}")
+        raise ValueError(f"{who}: data uint8 [n >= 1], seg_begin [F, {n_seg}]; got {tuple(data.shape)}, {tuple(seg_begin.shape)}")
     _chk_vec(seg_begin, "seg_begin", torch.int64, (F, n_seg)); _chk_vec(seg_end, "seg_end", torch.int64, (F, n_seg))
-    _chk_vec(htab_index, "htab_index", torch.int32, (F,)); _chk_vec(status, "status", torch.int32, (F,))
+    _chk_vec(htab_index, "htab_index", torch.int32, (F,))
     _chk(htabs, "htabs", torch.uint8)
     set_bytes = 6 * L.load().tg_jpeg_huff_table_bytes()
     if htabs.dim() != 2 or htabs.shape[0] < 1 or htabs.shape[1] != set_bytes or not htabs.is_contiguous():
-        raise ValueError(f"jpeg_decode_coeffs: htabs must be contiguous uint8 [sets, {set_bytes}], got {tuple(htabs.shape)}")
-    coef = torch.empty(F, rows * cols, bpm, 64, dtype=torch.int16, device=data.device)
+        raise ValueError(f"{who}: htabs must be contiguous uint8 [sets, {set_bytes}], got {tuple(htabs.shape)}")
+    return F, rows * cols, bpm
+
+
+def jpeg_decode_coeffs(data, seg_begin, seg_end, H, W, subsampling, restart_interval, htabs, htab_index, status):
+    """tg_jpeg_decode_coeffs: -> int16 [F, MCUs, blocks per MCU, 64], every coefficient written; htabs uint8 [sets, 6 * 912], htab_index int32 [F]; ORs into status."""
+    F, n_mcu, bpm = _chk_jpeg_decode_args("jpeg_decode_coeffs", data, seg_begin, seg_end, H, W, subsampling, restart_interval, htabs, htab_index)
+    _chk_vec(status, "status", torch.int32, (F,))
+    coef = torch.empty(F, n_mcu, bpm, 64, dtype=torch.int16, device=data.device)
     L.check(_launch("jpeg_decode_coeffs", L.load().tg_jpeg_decode_coeffs, _p(data), data.numel(), _p(seg_begin), _p(seg_end), F, H, W, JPEG_SUBSAMPLINGS[subsampling],
                     int(restart_interval), _p(htabs), htabs.shape[0], _p(htab_index), _p(coef), _p(status), _stream()), "tg_jpeg_decode_coeffs")
+    return coef
+
+
+JPEG_SYNC_SUB_BYTES = (16, 32, 64, 128, 256)
+
+
+def jpeg_decode_coeffs_sync(data, seg_begin, seg_end, H, W, subsampling, restart_interval, htabs, htab_index, sub_bytes, clean, rounds, coef=None):
+    """tg_jpeg_decode_coeffs_sync: the coefficients of jpeg_decode_coeffs, decoded in parallel inside every restart segment, sub_bytes raw bytes per lane; stores
+    clean (int32 [F]: 1 where the frame's coefficients are vouched for, 0 where the frame is to be decoded by jpeg_decode_coeffs) and rounds (int32 [F]); never
+    touches a status.  `coef`: a contiguous int16 [F, MCUs, blocks per MCU, 64] to fill instead of a new one."""
+    F, n_mcu, bpm = _chk_jpeg_decode_args("jpeg_decode_coeffs_sync", data, seg_begin, seg_end, H, W, subsampling, restart_interval, htabs, htab_index)
+    if isinstance(sub_bytes, bool) or sub_bytes not in JPEG_SYNC_SUB_BYTES:
+        raise ValueError(f"jpeg_decode_coeffs_sync: sub_bytes must be one of {JPEG_SYNC_SUB_BYTES}, got {sub_bytes!r}")
+    _chk_vec(clean, "clean", torch.int32, (F,)); _chk_vec(rounds, "rounds", torch.int32, (F,))
+    lib = L.load()
+    if coef is None:
+        coef = torch.empty(F, n_mcu, bpm, 64, dtype=torch.int16, device=data.device)
+    else:
+        _chk_vec(coef, "coef", torch.int16, (F, n_mcu, bpm, 64))
+    ws = torch.empty(max(lib.tg_jpeg_sync_ws_bytes(F, H, W, JPEG_SUBSAMPLINGS[subsampling], int(restart_interval)), 4), dtype=torch.uint8, device=data.device)
+    L.check(_launch("jpeg_decode_coeffs_sync", lib.tg_jpeg_decode_coeffs_sync, _p(data), data.numel(), _p(seg_begin), _p(seg_end), F, H, W,
+                    JPEG_SUBSAMPLINGS[subsampling], int(restart_interval), _p(htabs), htabs.shape[0], _p(htab_index), int(sub_bytes), _p(ws), ws.numel(), _p(coef),
+                    _p(clean), _p(rounds), _stream()), "tg_jpeg_decode_coeffs_sync")
     return coef
 
 

@@ -252,7 +252,8 @@ class VideoProcessor:
 def load_video(video_path, output_res, nf_per_chunk, pad_to_fit, sample_fps, start_t, end_t, max_num_chunks, crop_to_fit=False, device=None):
     """The first step of the reference's entry script (`load_video`, long_video.py:28-76, same parameter order): a Motion-JPEG .avi file (one that `export_to_video`
     wrote, or any baseline MJPG AVI) -> bf16 [1, F, 3, oh, ow] in [-1, 1] on the device.  The file's index is read on the host, `sample_frame_indices` picks the
-    frames, they are decoded on the device (tokensgen_amd.jpeg.MJPEGReader) and go through `prepare_video`.  Any other suffix is refused: there is no
+    frames, they are decoded on the device (tokensgen_amd.jpeg.MJPEGReader; a file without restart markers in parallel inside each frame, §8m) and go
+    through `prepare_video`.  Any other suffix is refused: there is no
     H.264 / mp4 decoder here.  The JPEG code is imported by the first call."""
     from . import jpeg
     return jpeg.load_video(video_path, output_res, nf_per_chunk, pad_to_fit, sample_fps, start_t, end_t, max_num_chunks, crop_to_fit, device)
