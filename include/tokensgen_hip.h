@@ -1045,6 +1045,45 @@ long tg_jpeg_idct_ws_bytes(int F, int H, int W, int subsampling);
 int tg_jpeg_idct_rgb(const void* coef, int F, int H, int W, int subsampling, const void* qtabs, int n_qsets, const void* qtab_index, void* ws, long ws_bytes, void* rgb,
                      long rgb_bytes, hipStream_t stream);
 
+/* Lossless PNG of the byte output (csrc/png.hip, csrc/png_deflate.h).  Integer arithmetic only: a frame is one exact byte string, the same alone and
+ * in a batch; tests/png_ref.py restates this comment in numpy.  Any PNG reader opens the files; nothing here reads one.
+ *   The file.  Signature; IHDR (W, H, bit depth 8, colour type 2, compression 0, filter 0, no interlace); one IDAT chunk per band of rows; IEND.  The zlib stream is the
+ *   concatenation of the IDAT payloads: the first begins with the zlib header 78 01, the last ends with the final block 03 00 (fixed Huffman, end of block only) and
+ *   the big-endian Adler-32 of the frame's filtered bytes.  Every chunk carries its own CRC-32.
+ *   Filtering.  bpp 3; the row above row 0 and the pixel left of pixel 0 are zeros; a filtered row is the type byte and 3 W bytes.  filter 0..4 (none, sub, up,
+ *   average, paeth) forces one type; 5 (adaptive): of the five filtered rows the one with the smallest sum of min(v, 256 - v) over its 3 W bytes, of equal sums the
+ *   lowest type.  Filters read raw neighbours only.
+ *   Bands.  rows_per_block consecutive rows (the last band of a frame may have fewer), at most 65535 bytes: hence W <= 21844.  rows_per_block 0: the default,
+ *   min(16, 65535 / (1 + 3 W)).
+ *   Tokens.  A band is cut into maximal runs of equal bytes; no token refers across a band.  A run of L bytes is its first byte as a literal, then floor((L - 1) / 258)
+ *   matches of length 258 at distance 1, then the remainder (L - 1) mod 258 as one more match if it is at least 3 and as one or two literals otherwise.
+ *   Coding.  A band is one dynamic-Huffman block (BFINAL 0, BTYPE 10) followed by an empty stored block (bits 000, zeros to the byte, 00 00 FF FF), so that a band's
+ *   output is whole bytes; or, where that is not SMALLER than 5 + n bytes, one stored block (00, LEN, NLEN, the n bytes).
+ *     Code lengths (limit 15 for literal/length, histogram of the tokens plus one end of block; limit 7 for the code-length alphabet): the symbols that occur, sorted
+ *     by (count, symbol) ascending, are the leaves of a Huffman tree built with two queues, the leaf taken before an internal node of equal weight; leaves deeper than
+ *     the limit are cut to it, and while the Kraft sum exceeds 1 (by k units of 2^-limit: k times) the step of zlib's gen_bitlen repays one unit: a leaf of the deepest
+ *     level below the limit that has one becomes an internal node with two children, one leaf of the limit goes; then the sorted symbols take the lengths from the
+ *     longest to the shortest.  One symbol alone: length 1.
+ *     Codes are canonical (RFC 1951 3.2.2).  The distance code is always the single symbol 0 with length 1 (HDIST 0).
+ *     The code-length sequence is the literal/length lengths up to the last used symbol and the distance length 1, as one sequence.  r zeros: symbol 18 (up to 138 at
+ *     a time) while r >= 11, then 17 if r >= 3, then single zeros.  r equal non-zero lengths: the length, then 16 (up to 6 at a time) while r >= 3 remain, then the
+ *     length itself for the rest.  HCLEN: up to the last used symbol in the order 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15, at least 4.
+ * tg_png_geometry(H, W, rows_per_block, what): 0 rows of a band, 1 bands of a frame, 2 bytes of a filtered row, 3 bytes of a frame in the filtered workspace (every band
+ *   starts at a multiple of 16), 4 bytes of a band's plan record, 5 an upper bound of a file's bytes, 6 / 7 the bytes in front of the first and behind the last IDAT
+ *   chunk of a file (33, 12); 0 for refused arguments (H 1..65535, W 1..21844, a band above 65535 bytes).  Pure host function.
+ * tg_png_filter: frames uint8 [F, H, W, 3] contiguous -> filtered (F * geometry 3 bytes, 16-byte aligned).
+ * tg_png_band_plan: filtered -> plans (F * bands records of geometry 4 bytes: the code lengths, stored or dynamic, the bytes, the band's Adler pair) and band_bytes int32
+ *   [F, bands]: the bytes of every band's IDAT chunk with its 12 bytes of framing, the zlib header (first band) and the final block and checksum (last band).
+ * tg_png_write: band_offsets int64 [F, bands]: where every band's chunk starts in data (8-byte aligned pointer).  The first band of a frame also writes the 33 bytes in
+ *   front of its chunk, the last band the 12 bytes behind it.  A band whose offset lies outside [0, data_bytes], or whose plan record does not describe it, is not
+ *   written; every store is checked against data_bytes.  Bands share no byte: no atomics on data, the bytes are the same in every run.
+ * None of the three allocates, copies or waits. */
+long tg_png_geometry(int H, int W, int rows_per_block, int what);
+int tg_png_filter(const void* frames, int F, int H, int W, int filter, int rows_per_block, void* filtered, hipStream_t stream);
+int tg_png_band_plan(const void* filtered, int F, int H, int W, int rows_per_block, void* plans, void* band_bytes, hipStream_t stream);
+int tg_png_write(const void* filtered, const void* plans, int F, int H, int W, int rows_per_block, const void* band_offsets, void* data, long data_bytes,
+                 hipStream_t stream);
+
 /* Dispatch overrides for the cross-check tests — NOT part of the operator surface.  The library reads no environment variable and keeps no other
  * process-wide state: the defaults are the shipped path, and these knobs only choose between two PRODUCT kernels of the same operator (each pair is held
  * bitwise or to rounding against each other by tests/).  Knobs: TG_ATTN_PP_MIN_WG (1024: workgroups from which the 8-wave attention kernel is used),

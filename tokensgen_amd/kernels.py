@@ -1597,3 +1597,57 @@ def jpeg_idct_rgb(coef, H, W, subsampling, qtabs, qtab_index, out=None):
     L.check(_launch("jpeg_idct_rgb", lib.tg_jpeg_idct_rgb, _p(coef), F, H, W, JPEG_SUBSAMPLINGS[subsampling], _p(qtabs), qtabs.shape[0], _p(qtab_index), _p(ws),
                     ws.numel(), _p(out), out.numel(), _stream()), "tg_jpeg_idct_rgb")
     return out
+
+
+PNG_FILTERS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}
+
+
+def png_geometry(H, W, rows_per_block=0):
+    """tg_png_geometry: (rows of a band, bands of a frame, bytes of a filtered row, bytes of a frame in the filtered workspace, bytes of a plan record, an upper bound of
+    a file's bytes, the bytes in front of the first and behind the last IDAT chunk); rows_per_block 0 is the default; refused arguments raise."""
+    lib = L.load()
+    g = tuple(lib.tg_png_geometry(H, W, rows_per_block, what) for what in range(8))
+    if not all(g):
+        raise ValueError(f"png: a frame of {H} (1..65535) x {W} (1..21844) with bands of rows_per_block {rows_per_block!r} rows, each at most 65535 bytes")
+    return g
+
+
+def png_filter(frames, filter, rows_per_block=0):
+    """tg_png_filter: contiguous uint8 [F, H, W, 3] -> uint8 [F, workspace bytes of a frame]: every row's filter type and filtered bytes, a band's rows together and
+    every band at a multiple of 16 bytes (the header's definition)."""
+    F, H, W = _chk_u8_frames(frames, "png_filter")
+    if filter not in PNG_FILTERS:
+        raise ValueError(f"png_filter: filter must be one of {tuple(PNG_FILTERS)}, got {filter!r}")
+    ws = png_geometry(H, W, rows_per_block)[3]
+    out = torch.empty(F, ws, dtype=torch.uint8, device=frames.device)
+    L.check(_launch("png_filter", L.load().tg_png_filter, _p(frames), F, H, W, PNG_FILTERS[filter], int(rows_per_block), _p(out), _stream()), "tg_png_filter")
+    return out
+
+
+def _chk_png_filtered(filtered, H, W, rows_per_block, who):
+    _chk(filtered, "filtered", torch.uint8)
+    g = png_geometry(H, W, rows_per_block)
+    if filtered.dim() != 2 or filtered.shape[1] != g[3] or filtered.shape[0] < 1 or not filtered.is_contiguous():
+        raise ValueError(f"{who}: filtered must be contiguous [F, {g[3]}], got {tuple(filtered.shape)}")
+    return filtered.shape[0], g
+
+
+def png_band_plan(filtered, H, W, rows_per_block=0):
+    """tg_png_band_plan: -> (plans uint8 [F, bands, record bytes], band_bytes int32 [F, bands]: every band's IDAT chunk with its framing)."""
+    F, g = _chk_png_filtered(filtered, H, W, rows_per_block, "png_band_plan")
+    plans = torch.empty(F, g[1], g[4], dtype=torch.uint8, device=filtered.device)
+    band_bytes = torch.empty(F, g[1], dtype=torch.int32, device=filtered.device)
+    L.check(_launch("png_band_plan", L.load().tg_png_band_plan, _p(filtered), F, H, W, int(rows_per_block), _p(plans), _p(band_bytes), _stream()), "tg_png_band_plan")
+    return plans, band_bytes
+
+
+def png_write(filtered, plans, H, W, rows_per_block, band_offsets, data):
+    """tg_png_write: every frame's file into `data` (uint8 [n]); band_offsets int64 [F, bands]: where every band's IDAT chunk starts."""
+    F, g = _chk_png_filtered(filtered, H, W, rows_per_block, "png_write")
+    _chk(plans, "plans", torch.uint8); _chk(band_offsets, "band_offsets", torch.int64); _chk(data, "data", torch.uint8)
+    if tuple(plans.shape) != (F, g[1], g[4]) or not plans.is_contiguous() or tuple(band_offsets.shape) != (F, g[1]) or not band_offsets.is_contiguous() or data.dim() != 1:
+        raise ValueError(f"png_write: plans contiguous [{F}, {g[1]}, {g[4]}], band_offsets contiguous [{F}, {g[1]}], data [n]; got {tuple(plans.shape)}, "
+                         f"{tuple(band_offsets.shape)}, {tuple(data.shape)}")
+    L.check(_launch("png_write", L.load().tg_png_write, _p(filtered), _p(plans), F, H, W, int(rows_per_block), _p(band_offsets), _p(data), data.numel(), _stream()),
+            "tg_png_write")
+    return data
