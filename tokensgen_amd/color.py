@@ -14,6 +14,7 @@ uint8 frames only ("uint8" of video_io.VideoProcessor, which runs this step afte
 import torch
 
 from . import kernels as K
+from .frames import check_frames, is_int
 
 MODES = tuple(K.COLOR_MODES)
 MAX_WINDOW = K.COLOR_MAX_WINDOW
@@ -24,26 +25,20 @@ def check_params(mode, strength, window, max_gain, who):
         raise ValueError(f"{who}: mode must be one of {MODES}, got {mode!r}")
     if isinstance(strength, bool) or not isinstance(strength, (int, float)) or not 0.0 <= strength <= 1.0:
         raise ValueError(f"{who}: strength must be a number in [0, 1], got {strength!r}")
-    if not isinstance(window, int) or isinstance(window, bool) or not 1 <= window <= MAX_WINDOW:
+    if not is_int(window) or not 1 <= window <= MAX_WINDOW:
         raise ValueError(f"{who}: window must be an integer in 1..{MAX_WINDOW}, got {window!r}")
     if isinstance(max_gain, bool) or not isinstance(max_gain, (int, float)) or not 1.0 <= max_gain < float("inf"):
         raise ValueError(f"{who}: max_gain must be a finite number >= 1, got {max_gain!r}")
 
 
 def check_anchor_frames(anchor_frames, who):
-    if not isinstance(anchor_frames, int) or isinstance(anchor_frames, bool) or anchor_frames < 1:
+    if not is_int(anchor_frames) or anchor_frames < 1:
         raise ValueError(f"{who}: anchor_frames must be a positive integer, got {anchor_frames!r}")
 
 
-def check_frames(frames, who, dims=(4, 5)):
-    """The shape contract of every entry point, checked before any kernel call."""
-    if not isinstance(frames, torch.Tensor):
-        raise ValueError(f"{who}: expected a tensor of frames")
-    if frames.dtype != torch.uint8:
-        raise NotImplementedError(f"{who}: uint8 frames only (video_io's \"uint8\" output), got {frames.dtype}")
-    if frames.dim() not in dims or frames.shape[-1] != 3 or frames.numel() < 1:
-        want = " or ".join({4: "[F, H, W, 3]", 5: "[B, T, H, W, 3]"}[d] for d in dims)
-        raise ValueError(f"{who}: expected {want} with at least one pixel, got {tuple(frames.shape)}")
+def check_color_frames(frames, who, dims=(4, 5)):
+    """frames.check_frames and what is colour's own: a frame's histogram counts are int32"""
+    check_frames(frames, who, dims)
     if frames.shape[-3] * frames.shape[-2] >= 1 << 31:
         raise ValueError(f"{who}: a frame of {frames.shape[-3]} x {frames.shape[-2]} pixels reaches 2^31")
 
@@ -57,7 +52,7 @@ def _check_hist(h, name, dtype, lead, who):
 def color_histograms(frames):
     """uint8 [F, H, W, 3] (or [B, T, H, W, 3]) -> int32 [F, 3, 256] ([B, T, 3, 256]): per frame and channel the number of pixels of each value.  Exact; a frame's
     counts depend on that frame alone.  A view that is not contiguous is copied first."""
-    check_frames(frames, "color_histograms")
+    check_color_frames(frames, "color_histograms")
     h = K.color_hist_u8(frames.contiguous().reshape(-1, *frames.shape[-3:]))
     return h.reshape(*frames.shape[:-3], 3, 256)
 
@@ -82,7 +77,7 @@ def match_luts(hist, anchor_hist, mode="meanstd", strength=1.0, window=1, max_ga
 def apply_luts(frames, luts, out=None):
     """out[f, y, x, c] = luts[f, c, frames[f, y, x, c]].  frames uint8 [F, H, W, 3] contiguous, luts uint8 [F, 3, 256]; out: None (a new tensor), `frames` (in place)
     or a contiguous tensor of the frames' shape."""
-    check_frames(frames, "apply_luts", dims=(4,))
+    check_color_frames(frames, "apply_luts", dims=(4,))
     if not isinstance(luts, torch.Tensor) or luts.dtype != torch.uint8 or tuple(luts.shape) != (frames.shape[0], 3, 256):
         raise ValueError(f"apply_luts: luts must be uint8 [{frames.shape[0]}, 3, 256], got {getattr(luts, 'dtype', type(luts))} {tuple(getattr(luts, 'shape', ()))}")
     if not frames.is_contiguous():
@@ -120,7 +115,7 @@ def match_colors(frames, anchor=None, anchor_frames=8, mode="meanstd", strength=
     histograms are summed; an int64 [3, 256] histogram; or None: the first min(T, anchor_frames) frames of the video itself.  Returns the matched uint8 video (a new
     tensor), or with return_luts (video, luts uint8 [.., T, 3, 256]).  With strength 0, or with mode "histogram" and an anchor equal to the source, the output is
     the input byte for byte.  Nothing here waits for the device."""
-    check_frames(frames, "match_colors")
+    check_color_frames(frames, "match_colors")
     check_params(mode, strength, window, max_gain, "match_colors")
     check_anchor_frames(anchor_frames, "match_colors")
     check_anchor(anchor, "match_colors")
@@ -156,7 +151,7 @@ class ColorMatcher:
         self._ready, self._history = False, None
 
     def update(self, frames):
-        check_frames(frames, "ColorMatcher.update", dims=(4,))
+        check_color_frames(frames, "ColorMatcher.update", dims=(4,))
         _check_window_total(self.window, frames.shape[1], frames.shape[2], "ColorMatcher.update")
         if not self._ready and self._anchor is None and frames.shape[0] < self.anchor_frames:
             raise ValueError(f"ColorMatcher.update: the first clip of a video must carry the {self.anchor_frames} anchor frames, got {frames.shape[0]} (no lookahead)")

@@ -1,5 +1,5 @@
 """The byte output as files: a baseline-JPEG encoder on the GPU (tg_jpeg_coeffs, tg_jpeg_segment_bytes, tg_jpeg_write, csrc/jpeg.hip) and a Motion-JPEG AVI writer
-in plain Python around it; DESIGN.md §8k.  No reference code: the header's comment is the definition, tests/jpeg_ref.py restates it, tests/avi_ref.py walks the file.
+in plain Python around it (the container itself: avi.py; the frame contract: frames.py); DESIGN.md §8k.  No reference code: the header's comment is the definition, tests/jpeg_ref.py restates it, tests/avi_ref.py walks the file.
 
     from tokensgen_amd.jpeg import encode_jpeg, save_jpeg, MJPEGWriter, write_mjpeg_avi
 
@@ -21,47 +21,32 @@ import functools
 import os
 import re
 import struct
-from fractions import Fraction
 from typing import NamedTuple
 
 import numpy as np
 import torch
 
+from . import avi
 from . import kernels as K
+from .frames import check_device, check_frames, gpu_device, is_int, single_frame, split_bytes
 
 SUBSAMPLINGS = tuple(K.JPEG_SUBSAMPLINGS)
 
 
-def _is_int(v):
-    return isinstance(v, int) and not isinstance(v, bool)
-
-
 def check_params(quality, subsampling, restart_interval, who):
-    if not _is_int(quality) or not 1 <= quality <= 100:
+    if not is_int(quality) or not 1 <= quality <= 100:
         raise ValueError(f"{who}: quality must be an integer in 1..100, got {quality!r}")
     if subsampling not in SUBSAMPLINGS:
         raise ValueError(f"{who}: subsampling must be one of {SUBSAMPLINGS}, got {subsampling!r}")
-    if not _is_int(restart_interval) or not 1 <= restart_interval <= 65535:
+    if not is_int(restart_interval) or not 1 <= restart_interval <= 65535:
         raise ValueError(f"{who}: restart_interval must be an integer in 1..65535, got {restart_interval!r}")
 
 
-def check_frames(frames, who, dims=(4, 5)):
-    """The shape contract of every entry point, checked before any kernel call."""
-    if not isinstance(frames, torch.Tensor):
-        raise ValueError(f"{who}: expected a tensor of frames")
-    if frames.dtype != torch.uint8:
-        raise NotImplementedError(f"{who}: uint8 frames only (video_io's \"uint8\" output), got {frames.dtype}")
-    want = " or ".join({3: "[H, W, 3]", 4: "[F, H, W, 3]", 5: "[B, T, H, W, 3]"}[d] for d in dims)
-    if frames.dim() not in dims or frames.shape[-1] != 3 or frames.numel() < 1:
-        raise ValueError(f"{who}: expected {want} (RGB, three channels) with at least one pixel, got {tuple(frames.shape)}")
+def check_jpeg_frames(frames, who, dims=(4, 5)):
+    """frames.check_frames and what is JPEG's own: SOF0 holds a frame's sides in 16 bits"""
+    check_frames(frames, who, dims)
     if frames.shape[-3] > 65535 or frames.shape[-2] > 65535:
         raise ValueError(f"{who}: a JPEG frame is at most 65535 x 65535, got {frames.shape[-3]} x {frames.shape[-2]}")
-
-
-def check_device(frames, who):
-    """after every other check, so that a wrong argument is named with or without a device"""
-    if not frames.is_cuda:
-        raise RuntimeError(f"{who}: expected a GPU tensor (tokensgen_amd has no CPU path)")
 
 
 def stream_offsets(seg_bytes, header):
@@ -78,7 +63,7 @@ def encode_jpeg(frames, quality=90, subsampling="420", restart_interval=1):
     """uint8 [F, H, W, 3] (or [B, T, H, W, 3], frames in order) on the device -> (data, offsets): data a uint8 device tensor of exactly offsets[-1] bytes, offsets int64
     [F + 1] on the host; frame f is data[offsets[f]:offsets[f + 1]], a complete baseline JPEG.  subsampling "420" or "444"; restart_interval in MCUs: 1 (the default)
     gives the entropy pass one lane per MCU, a larger one a smaller file and less parallel work.  A view that is not contiguous is copied first."""
-    check_frames(frames, "encode_jpeg")
+    check_jpeg_frames(frames, "encode_jpeg")
     check_params(quality, subsampling, restart_interval, "encode_jpeg")
     check_device(frames, "encode_jpeg")
     H, W = frames.shape[-3:-1]
@@ -95,66 +80,40 @@ def encode_jpeg(frames, quality=90, subsampling="420", restart_interval=1):
 
 def jpeg_bytes(frames, quality=90, subsampling="420", restart_interval=1):
     """encode_jpeg, copied to the host and cut: a list of one `bytes` per frame."""
-    data, offsets = encode_jpeg(frames, quality, subsampling, restart_interval)
-    host, o = data.cpu().numpy().tobytes(), offsets.tolist()
-    return [host[o[i]:o[i + 1]] for i in range(len(o) - 1)]
+    return split_bytes(*encode_jpeg(frames, quality, subsampling, restart_interval))
 
 
 def save_jpeg(frame, path, quality=90, subsampling="420", restart_interval=1):
     """One frame, uint8 [H, W, 3] (or [1, H, W, 3]) on the device, as a .jpg file."""
-    check_frames(frame, "save_jpeg", dims=(3, 4))
-    if frame.dim() == 4 and frame.shape[0] != 1:
-        raise ValueError(f"save_jpeg: one frame per file, got {frame.shape[0]}")
+    check_jpeg_frames(frame, "save_jpeg", dims=(3, 4))
+    one = single_frame(frame, "save_jpeg")
     check_params(quality, subsampling, restart_interval, "save_jpeg")
     check_device(frame, "save_jpeg")
-    (b,) = jpeg_bytes(frame.reshape(1, *frame.shape[-3:]), quality, subsampling, restart_interval)
+    (b,) = jpeg_bytes(one, quality, subsampling, restart_interval)
     with open(path, "wb") as fh:
         fh.write(b)
     return path
 
 
-AVIF_HASINDEX, AVIIF_KEYFRAME = 0x10, 0x10
-_MOVI_FOURCC = 220                              # RIFF 12, LIST hdrl 8 + 192, LIST movi 8: where the 'movi' fourcc stands; the first chunk follows at 224
+class MJPEGWriter(avi.AVIWriter):
+    """A Motion-JPEG AVI 1.0 file, written as the frames arrive (the container: avi.AVIWriter).  `write(frames)` (uint8 [F, H, W, 3] or [B, T, H, W, 3] on the
+    device) or `write_jpegs` any number of times, then `close()`, which writes the index and the counts and sizes of the headers; or use it as a context manager.
+    All frames of a file have one size.  fps is any positive number: dwRate / dwScale = Fraction(fps).limit_denominator(65535).  A `write` that would take the file
+    past MAX_FILE_BYTES (2^31 - 1: no OpenDML) is refused whole with a ValueError, and `close()` still leaves a valid file of the frames before it."""
 
-
-class MJPEGWriter:
-    """A Motion-JPEG AVI 1.0 file, written as the frames arrive: RIFF 'AVI ' { LIST 'hdrl' { avih, LIST 'strl' { strh vids/MJPG, strf BITMAPINFOHEADER } }, LIST 'movi'
-    { 00dc chunks, padded to even length }, idx1 }.  `write(frames)` (uint8 [F, H, W, 3] or [B, T, H, W, 3] on the device) any number of times, then `close()`, which
-    writes the index and the counts and sizes of the headers; or use it as a context manager.  All frames of a file have one size.  fps is any positive number:
-    dwRate / dwScale = Fraction(fps).limit_denominator(65535).  A `write` that would take the file past MAX_FILE_BYTES (2^31 - 1: no OpenDML) is refused whole with
-    a ValueError, and `close()` still leaves a valid file of the frames before it."""
-
-    MAX_FILE_BYTES = (1 << 31) - 1
     BATCH = 64                                  # frames per encode call: bounds the coefficient workspace of a long video
 
     def __init__(self, path, fps, quality=90, subsampling="420", restart_interval=1):
         check_params(quality, subsampling, restart_interval, "MJPEGWriter")
-        if isinstance(fps, bool) or not isinstance(fps, (int, float, Fraction)) or not 0 < fps < float("inf"):
-            raise ValueError(f"MJPEGWriter: fps must be a positive finite number, got {fps!r}")
-        rate = Fraction(fps).limit_denominator(65535)
-        if rate <= 0 or rate.numerator >= 1 << 32:
-            raise ValueError(f"MJPEGWriter: fps {fps!r} has no dwRate / dwScale")
-        self.path, self.rate, self.quality, self.subsampling, self.restart_interval = path, rate, quality, subsampling, restart_interval
-        self.size = None                        # (H, W) of the first frame
-        self._index = []                        # (offset from the 'movi' fourcc, bytes) per frame
-        self._pos = _MOVI_FOURCC + 4            # file position == bytes so far
-        self._fh = open(path, "wb")
-        self._fh.write(b"\0" * self._pos)       # the headers are written by close(), when the counts are known
-
-    @property
-    def frames(self):
-        return len(self._index)
-
-    def _final_bytes(self, pos, n):
-        return pos + 8 + 16 * n
+        super().__init__(path, fps)
+        self.quality, self.subsampling, self.restart_interval = quality, subsampling, restart_interval
 
     def write(self, frames):
         if self._fh is None:
             raise ValueError("MJPEGWriter.write: the file is closed")
-        check_frames(frames, "MJPEGWriter.write")
+        check_jpeg_frames(frames, "MJPEGWriter.write")
         H, W = frames.shape[-3:-1]
-        if self.size is not None and self.size != (H, W):
-            raise ValueError(f"MJPEGWriter: all frames of a file have one size; the file holds {self.size[0]} x {self.size[1]}, got {H} x {W}")
+        self.check_size(H, W)
         check_device(frames, "MJPEGWriter.write")
         src = frames.reshape(-1, H, W, 3)
         chunks = []
@@ -162,60 +121,10 @@ class MJPEGWriter:
             chunks += jpeg_bytes(src[i:i + self.BATCH], self.quality, self.subsampling, self.restart_interval)
         return self.write_jpegs(chunks, H, W)
 
-    def write_jpegs(self, chunks, height, width):
-        """Frames that are JPEG streams already (a list of bytes, each of a height x width frame; what `jpeg_bytes` returns), as `write` appends them."""
-        if self._fh is None:
-            raise ValueError("MJPEGWriter.write_jpegs: the file is closed")
-        H, W = int(height), int(width)
-        if not 1 <= H <= 65535 or not 1 <= W <= 65535 or any(not isinstance(c, (bytes, bytearray)) or c[:2] != b"\xff\xd8" or c[-2:] != b"\xff\xd9" for c in chunks):
-            raise ValueError("MJPEGWriter.write_jpegs: expected JPEG streams (SOI .. EOI) of one height x width in 1..65535")
-        if self.size is not None and self.size != (H, W):
-            raise ValueError(f"MJPEGWriter: all frames of a file have one size; the file holds {self.size[0]} x {self.size[1]}, got {H} x {W}")
-        pos = self._pos + sum(8 + len(c) + (len(c) & 1) for c in chunks)
-        if self._final_bytes(pos, len(self._index) + len(chunks)) > self.MAX_FILE_BYTES:
-            raise ValueError(f"MJPEGWriter: {len(chunks)} more frames would take {self.path} past {self.MAX_FILE_BYTES} bytes (AVI 1.0, no OpenDML); "
-                             f"the file keeps its {len(self._index)} frames")
-        self.size = (H, W)
-        for c in chunks:
-            self._index.append((self._pos - _MOVI_FOURCC, len(c)))
-            self._fh.write(b"00dc" + struct.pack("<I", len(c)) + bytes(c) + b"\0" * (len(c) & 1))
-            self._pos += 8 + len(c) + (len(c) & 1)
-        return len(chunks)
-
-    def close(self):
-        if self._fh is None:
-            return
-        fh, self._fh = self._fh, None
-        n, (H, W) = len(self._index), self.size or (0, 0)
-        largest = max((s for _, s in self._index), default=0)
-        fh.write(b"idx1" + struct.pack("<I", 16 * n) + b"".join(b"00dc" + struct.pack("<III", AVIIF_KEYFRAME, o, s) for o, s in self._index))
-        total = self._final_bytes(self._pos, n)
-        rate, scale = self.rate.numerator, self.rate.denominator
-        avih = struct.pack("<14I", round(1e6 * scale / rate), min(int(largest * rate / scale) + 1, 0xffffffff) if n else 0, 0, AVIF_HASINDEX, n, 0, 1, largest, W, H,
-                           0, 0, 0, 0)
-        strh = b"vidsMJPG" + struct.pack("<IHHIIIIIIIIhhhh", 0, 0, 0, 0, scale, rate, 0, n, largest, 0xffffffff, 0, 0, 0, min(W, 32767),
-                                        min(H, 32767))
-        strf = struct.pack("<IiiHH4sIiiII", 40, W, H, 1, 24, b"MJPG", min(3 * W * H, 0xffffffff), 0, 0, 0, 0)
-        strl = b"LIST" + struct.pack("<I", 4 + 8 + len(strh) + 8 + len(strf)) + b"strl" + b"strh" + struct.pack("<I", len(strh)) + strh + b"strf" + \
-            struct.pack("<I", len(strf)) + strf
-        hdrl = b"LIST" + struct.pack("<I", 4 + 8 + len(avih) + len(strl)) + b"hdrl" + b"avih" + struct.pack("<I", len(avih)) + avih + strl
-        head = b"RIFF" + struct.pack("<I", total - 8) + b"AVI " + hdrl + b"LIST" + struct.pack("<I", self._pos - _MOVI_FOURCC) + b"movi"
-        assert len(head) == _MOVI_FOURCC + 4
-        fh.seek(0)
-        fh.write(head)
-        fh.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
 
 def write_mjpeg_avi(path, frames, fps, quality=90, subsampling="420", restart_interval=1):
     """All frames of one tensor as one Motion-JPEG AVI file; returns the path."""
-    check_frames(frames, "write_mjpeg_avi")
+    check_jpeg_frames(frames, "write_mjpeg_avi")
     check_device(frames, "write_mjpeg_avi")
     with MJPEGWriter(path, fps, quality, subsampling, restart_interval) as w:
         w.write(frames)
@@ -448,7 +357,7 @@ def entropy_plan(H, W, subsampling, restart_interval):
     ("sync", sub_bytes), parallel decoding inside every segment (tg_jpeg_decode_coeffs_sync).  A pure function of the geometry, no device call.  "sync" where a
     segment holds at least SYNC_MIN_MCUS MCUs; a frame that is one segment (no markers, or an interval of at least its MCUs) qualifies from two MCUs on: one MCU is too
     small to cut.  restart_interval 0: no markers."""
-    if not _is_int(restart_interval) or not 0 <= restart_interval <= 65535:
+    if not is_int(restart_interval) or not 0 <= restart_interval <= 65535:
         raise ValueError(f"entropy_plan: restart_interval must be an integer in 0..65535, got {restart_interval!r}")
     rows, cols, _, _ = K.jpeg_geometry(H, W, subsampling)
     n_mcu = rows * cols
@@ -480,7 +389,7 @@ def decode_jpeg(data, offsets=None, device=None, entropy="auto"):
             raise ValueError(f"{who}: all frames of a call share size, subsampling and restart interval; frame 0 is {first.height} x {first.width} {first.subsampling} "
                              f"interval {first.restart_interval}, frame {i} is {info.height} x {info.width} {info.subsampling} interval {info.restart_interval}")
     H, W, sub, ri = first[:4]
-    dev = _gpu(device if device is not None else (on_device.device if on_device is not None else None), who)
+    dev = gpu_device(device if device is not None else (on_device.device if on_device is not None else None), who)
     hsets, qsets, hidx, qidx = {}, {}, [], []
     for i, info in enumerate(infos):
         try:
@@ -509,20 +418,22 @@ def decode_jpeg(data, offsets=None, device=None, entropy="auto"):
     htabs, qtabs = cut(4, torch.uint8).view(len(hsets), -1), cut(5, torch.uint16).view(len(qsets), 3, 64)
     n_seg = K.jpeg_decode_segments(H, W, sub, ri)
     mode, sub_bytes = entropy_plan(H, W, sub, ri) if entropy == "auto" else (entropy, SYNC_SUB_BYTES)
+
+    def launch(status, entropy_launch):
+        """find the segments (which stores status), decode their coefficients by `entropy_launch`, transform: three launches, no wait"""
+        seg_begin, seg_end = K.jpeg_find_segments(stream_dev, scan_begin, scan_end, n_seg, status)
+        coef = entropy_launch(stream_dev, seg_begin, seg_end, H, W, sub, ri, htabs, htab_index)
+        return K.jpeg_idct_rgb(coef, H, W, sub, qtabs, qtab_index)
+
     if mode == "sync":
         flags = torch.empty(3 * F, dtype=torch.int32, device=dev)               # status, clean and rounds: one buffer, one read
-        status, clean, rounds = flags[:F], flags[F:2 * F], flags[2 * F:]
-        seg_begin, seg_end = K.jpeg_find_segments(stream_dev, scan_begin, scan_end, n_seg, status)
-        coef = K.jpeg_decode_coeffs_sync(stream_dev, seg_begin, seg_end, H, W, sub, ri, htabs, htab_index, sub_bytes, clean, rounds)
-        out = K.jpeg_idct_rgb(coef, H, W, sub, qtabs, qtab_index)
+        out = launch(flags[:F], lambda *args: K.jpeg_decode_coeffs_sync(*args, sub_bytes, flags[F:2 * F], flags[2 * F:]))
         got = flags.cpu()                                                       # the one wait of the call
         if not bool(got[:F].any()) and bool((got[F:2 * F] == 1).all()):
             return out
         # not vouched for: the serial decoder decides, and its status, frames and error text are the result
     status = torch.empty(F, dtype=torch.int32, device=dev)
-    seg_begin, seg_end = K.jpeg_find_segments(stream_dev, scan_begin, scan_end, n_seg, status)
-    coef = K.jpeg_decode_coeffs(stream_dev, seg_begin, seg_end, H, W, sub, ri, htabs, htab_index, status)
-    out = K.jpeg_idct_rgb(coef, H, W, sub, qtabs, qtab_index)
+    out = launch(status, lambda *args: K.jpeg_decode_coeffs(*args, status))
     st = status.cpu()                                                           # the one wait of the call
     if bool(st.any()):
         f = int(torch.nonzero(st)[0])
@@ -532,198 +443,31 @@ def decode_jpeg(data, offsets=None, device=None, entropy="auto"):
     return out
 
 
-def _gpu(device, who):
-    dev = torch.device(device) if device is not None else None
-    if dev is None:
-        if not torch.cuda.is_available():
-            raise RuntimeError(f"{who}: needs a GPU (tokensgen_amd has no CPU path)")
-        return torch.device("cuda", torch.cuda.current_device())
-    if dev.type != "cuda":
-        raise RuntimeError(f"{who}: needs a GPU device, got {dev} (tokensgen_amd has no CPU path)")
-    return torch.device("cuda", torch.cuda.current_device()) if dev.index is None and torch.cuda.is_available() else dev
-
-
 def load_jpeg(path, device=None):
     """One baseline .jpg file -> uint8 [H, W, 3] on the device; a file without restart markers is decoded in parallel inside the frame (entropy_plan)."""
     with open(path, "rb") as fh:
         return decode_jpeg([fh.read()], device=device)[0]
 
 
-def _avi_bad(path, what):
-    return ValueError(f"MJPEGReader: {path}: {what}")
-
-
-class MJPEGReader:
-    """A Motion-JPEG AVI 1.0 file (ours, or any baseline MJPG AVI): `.frames` / len(), `.size` (H, W), `.fps` (a Fraction, dwRate / dwScale), `get_avg_fps()`;
-    `get_batch(indices)` and `read(start=0, stop=None)` return uint8 [n, H, W, 3] on the device, decoded at most BATCH frames per decode_jpeg call (entropy "auto":
-    frames without restart markers are decoded in parallel inside the frame); an index may repeat.
-    The first `strl` whose `strh` is `vids` with handler or biCompression MJPG is the stream; its NNdc / NNdb chunks are the frames, other streams' chunks are skipped,
-    LIST 'rec ' is walked.  `idx1` is used when present (offsets relative to the 'movi' fourcc or to the file: whichever finds the chunk's fourcc), otherwise `movi` is
-    walked.  A chunk of length 0 repeats the frame before it.  OpenDML (RIFF AVIX, indx) and other codecs are refused by name; a truncated file is a ValueError.  The
-    constructor reads the headers and the index only; the frames are read from the file when asked for.  A context manager."""
+class MJPEGReader(avi.AVIReader):
+    """A Motion-JPEG AVI 1.0 file (ours, or any baseline MJPG AVI; the container and what it takes and refuses: avi.AVIReader): `.frames` / len(), `.size` (H, W),
+    `.fps` (a Fraction, dwRate / dwScale), `get_avg_fps()`; `get_batch(indices)` and `read(start=0, stop=None)` return uint8 [n, H, W, 3] on the device, decoded at
+    most BATCH frames per decode_jpeg call (entropy "auto": frames without restart markers are decoded in parallel inside the frame); an index may repeat.  The
+    constructor reads the headers, the index and the first frame's headers, which say the size; the frames are read from the file when asked for.  A context
+    manager."""
 
     BATCH = 64
 
     def __init__(self, path, device=None):
-        self.path, self.device = path, device
-        self._fh = open(path, "rb")
-        try:
-            self._parse()
-        except BaseException:
-            self.close()
-            raise
-
-    def _parse(self):
-        fh, path = self._fh, self.path
-        fh.seek(0, os.SEEK_END)
-        size = fh.tell()
-        fh.seek(0)
-
-        def read_at(pos, n, what):
-            if pos < 0 or pos + n > size:
-                raise _avi_bad(path, f"the file is truncated: {what} at byte {pos} needs {n} bytes, the file has {size}")
-            fh.seek(pos)
-            return fh.read(n)
-
-        head = read_at(0, 12, "the RIFF header")
-        if head[:4] != b"RIFF" or head[8:12] != b"AVI ":
-            raise _avi_bad(path, "not a RIFF 'AVI ' file")
-        riff_end = 8 + struct.unpack_from("<I", head, 4)[0]
-        if riff_end > size:
-            raise _avi_bad(path, f"the file is truncated: RIFF says {riff_end} bytes, the file has {size}")
-        after = riff_end + (riff_end & 1)
-        if after + 12 <= size and read_at(after, 12, "a second RIFF")[8:12] == b"AVIX":
-            raise NotImplementedError(f"MJPEGReader: {path}: OpenDML (a RIFF 'AVIX' extension); AVI 1.0 only")
-        stream, rate, scale, dims, movi, idx1 = None, None, None, None, None, None
-        pos = 12
-        while pos + 8 <= riff_end:
-            fourcc, n = struct.unpack("<4sI", read_at(pos, 8, "a chunk header"))
-            if pos + 8 + n > riff_end:
-                raise _avi_bad(path, f"the file is truncated: chunk {fourcc!r} at byte {pos} ({n} bytes) runs past the end at {riff_end}")
-            if fourcc == b"LIST":
-                kind = read_at(pos + 8, 4, "a LIST type")
-                if kind == b"hdrl":
-                    stream, rate, scale, dims = self._parse_hdrl(read_at(pos + 12, n - 4, "the header list"))
-                elif kind == b"movi":
-                    movi = (pos + 8, pos + 8 + n)                               # from the 'movi' fourcc to the end of the list
-            elif fourcc == b"idx1":
-                idx1 = (pos + 8, n)
-            pos += 8 + n + (n & 1)
-        if stream is None:
-            raise NotImplementedError(f"MJPEGReader: {path}: no video stream with codec MJPG (handler or biCompression); Motion-JPEG only")
-        if movi is None:
-            raise _avi_bad(path, "no LIST 'movi'")
-        tags = (b"%02ddc" % stream, b"%02ddb" % stream)
-        entries = []                                                            # (payload position, bytes)
-        if idx1 is not None and idx1[1] >= 16:
-            raw = read_at(idx1[0], idx1[1] - idx1[1] % 16, "idx1")
-            rows = [struct.unpack_from("<4sIII", raw, i) for i in range(0, len(raw), 16)]
-            ours = [r for r in rows if r[0] in tags]
-            base = None
-            if ours:
-                for cand in (movi[0], 0):                                       # relative to the 'movi' fourcc, or to the file
-                    p = cand + ours[0][2]
-                    if 0 <= p and p + 8 <= size and read_at(p, 4, "an indexed chunk") == ours[0][0]:
-                        base = cand
-                        break
-                if base is None:
-                    raise _avi_bad(path, "idx1 does not point at the first frame's chunk, from the 'movi' list or from the file start")
-            for fourcc, _, off, n in ours:
-                if base + off + 8 + n > size:
-                    raise _avi_bad(path, f"the file is truncated: an indexed frame at byte {base + off} ({n} bytes) runs past the end at {size}")
-                entries.append((base + off + 8, n))
-        else:
-            self._walk(read_at, movi[0] + 4, movi[1], tags, entries)
-        self._entries = []
-        for i, (p, n) in enumerate(entries):
-            if n == 0:
-                if not self._entries:
-                    raise _avi_bad(path, "the first frame is a zero-length chunk: there is no frame before it to repeat")
-                self._entries.append(self._entries[-1])
-            else:
-                self._entries.append((p, n))
-        self.fps = Fraction(rate, scale)
-        self.size = dims
+        super().__init__(path)
+        self.device = device
         if self._entries:
-            p, n = self._entries[0]
-            info = parse_jpeg(read_at(p, n, "the first frame"), 0)
+            try:
+                info = parse_jpeg(self._read_at(*self._entries[0], "the first frame"), 0)
+            except BaseException:
+                self.close()
+                raise
             self.size = (info.height, info.width)
-
-    @staticmethod
-    def _parse_hdrl(buf):
-        """-> (stream number, dwRate, dwScale, (H, W)) of the first MJPG video stream, or (None, ..)"""
-        pos, number = 0, 0
-        while pos + 8 <= len(buf):
-            fourcc, n = struct.unpack_from("<4sI", buf, pos)
-            if fourcc == b"LIST" and buf[pos + 8:pos + 12] == b"strl":
-                strh = strf = None
-                has_indx = False
-                q, end = pos + 12, min(pos + 8 + n, len(buf))
-                while q + 8 <= end:
-                    cc, m = struct.unpack_from("<4sI", buf, q)
-                    if cc == b"strh":
-                        strh = buf[q + 8:q + 8 + m]
-                    elif cc == b"strf":
-                        strf = buf[q + 8:q + 8 + m]
-                    elif cc == b"indx":
-                        has_indx = True
-                    q += 8 + m + (m & 1)
-                if strh is not None and len(strh) >= 28 and strh[:4] == b"vids":
-                    codec = strf[16:20] if strf is not None and len(strf) >= 20 else b""
-                    if strh[4:8].upper() == b"MJPG" or codec.upper() == b"MJPG":
-                        if has_indx:
-                            raise NotImplementedError("MJPEGReader: OpenDML (an 'indx' super index in the stream header); AVI 1.0 only")
-                        scale, rate = struct.unpack_from("<II", strh, 20)
-                        if scale < 1 or rate < 1:
-                            raise ValueError(f"MJPEGReader: the stream header has no frame rate (dwRate {rate} / dwScale {scale})")
-                        dims = struct.unpack_from("<ii", strf, 4) if strf is not None and len(strf) >= 12 else (0, 0)
-                        return number, rate, scale, (abs(dims[1]), dims[0])
-                    raise NotImplementedError(f"MJPEGReader: video codec {strh[4:8]!r} / {codec!r}; Motion-JPEG (MJPG) only")
-                number += 1
-            pos += 8 + n + (n & 1)
-        return None, None, None, None
-
-    def _walk(self, read_at, pos, end, tags, entries):
-        while pos + 8 <= end:
-            fourcc, n = struct.unpack("<4sI", read_at(pos, 8, "a chunk header"))
-            if pos + 8 + n > end:
-                raise _avi_bad(self.path, f"the file is truncated: chunk {fourcc!r} at byte {pos} ({n} bytes) runs past the end of 'movi' at {end}")
-            if fourcc == b"LIST":
-                if read_at(pos + 8, 4, "a LIST type") == b"rec ":
-                    self._walk(read_at, pos + 12, pos + 8 + n, tags, entries)
-            elif fourcc in tags:
-                entries.append((pos + 8, n))
-            elif fourcc[:2] == b"ix":
-                raise NotImplementedError(f"MJPEGReader: {self.path}: OpenDML (an '{fourcc.decode('latin1')}' index chunk); AVI 1.0 only")
-            pos += 8 + n + (n & 1)
-
-    @property
-    def frames(self):
-        return len(self._entries)
-
-    def __len__(self):
-        return len(self._entries)
-
-    def get_avg_fps(self):
-        return float(self.fps)
-
-    def frame_bytes(self, indices):
-        """the JPEG streams of those frames, from the file"""
-        if self._fh is None:
-            raise ValueError("MJPEGReader: the file is closed")
-        out, cache = [], {}
-        for i in indices:
-            i = int(i)
-            if not -len(self) <= i < len(self):
-                raise IndexError(f"MJPEGReader: frame {i} of {len(self)}")
-            p, n = self._entries[i]
-            if p not in cache:
-                self._fh.seek(p)
-                cache[p] = self._fh.read(n)
-                if len(cache[p]) != n:
-                    raise _avi_bad(self.path, f"the file is truncated: frame {i} at byte {p} has {len(cache[p])} of {n} bytes")
-            out.append(cache[p])
-        return out
 
     def get_batch(self, indices):
         """uint8 [len(indices), H, W, 3] on the device"""
@@ -753,18 +497,6 @@ class MJPEGReader:
     def read(self, start=0, stop=None):
         return self.get_batch(range(*slice(start, stop).indices(len(self))))
 
-    def close(self):
-        if self._fh is not None:
-            self._fh.close()
-            self._fh = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
 
 def read_mjpeg_avi(path, device=None):
     """All frames of one Motion-JPEG AVI file: (uint8 [F, H, W, 3] on the device, fps as a Fraction)."""
@@ -789,7 +521,7 @@ def export_to_video(video_frames, output_video_path, fps=8, quality=90):
     ext = os.path.splitext(str(output_video_path))[1].lower()
     if ext != ".avi":
         raise ValueError(f"export_to_video: {output_video_path!r}: only the Motion-JPEG .avi format is written (no {ext or 'suffix-less'} encoder here)")
-    check_frames(video_frames, "export_to_video")
+    check_jpeg_frames(video_frames, "export_to_video")
     if video_frames.dim() == 5 and video_frames.shape[0] != 1:
         raise ValueError(f"export_to_video: one video per file, got a batch of {video_frames.shape[0]}; pass video[i]")
     check_device(video_frames, "export_to_video")

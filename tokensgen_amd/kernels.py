@@ -871,19 +871,41 @@ def tile_blend(a, b, axis, extent):
     return b
 
 
+def _chk_vec(t, name, dtype, shape):
+    """this dtype, exactly this shape, contiguous, on the GPU"""
+    _chk(t, name, dtype)
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{name}: expected contiguous {list(shape)}, got {tuple(t.shape)}")
+
+
+def _chk_rgb(t, name, contiguous=False):
+    """uint8 RGB frames on the GPU, [F, H, W, 3] or [B, T, H, W, 3], any view; with `contiguous` only a contiguous [F, H, W, 3] with at least one pixel and frames
+    below 2^31 pixels.  -> (n_outer, n_inner, H, W) and the byte strides (outer, inner, row, pixel, channel)"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{name}: expected a GPU tensor (tokensgen_amd has no CPU fallback)")
+    want = "contiguous uint8 [F, H, W, 3] with at least one pixel" if contiguous else "uint8 [F, H, W, 3] or [B, T, H, W, 3] with non-negative strides"
+    if t.dtype != torch.uint8 or t.dim() not in ((4,) if contiguous else (4, 5)) or t.shape[-1] != 3 or min(t.stride()) < 0 or \
+            (contiguous and (not t.is_contiguous() or t.numel() < 1)):
+        raise ValueError(f"{name}: expected {want}, got {t.dtype} {tuple(t.shape)}")
+    if contiguous and t.shape[1] * t.shape[2] >= 1 << 31:
+        raise ValueError(f"{name}: a frame of {t.shape[1]} x {t.shape[2]} pixels reaches 2^31")
+    s = t.stride()
+    if t.dim() == 4:
+        return (1, t.shape[0], t.shape[1], t.shape[2]), (0, s[0], s[1], s[2], s[3])
+    return (t.shape[0], t.shape[1], t.shape[2], t.shape[3]), (s[0], s[1], s[2], s[3], s[4])
+
+
 def video_resample(frames_u8, tables, oh, ow):
     """tg_video_resample: uint8 [F, H, W, 3] contiguous -> bf16 [F, 3, oh, ow] in [-1, 1].  tables = (y0, ny, wy, x0, nx, wx) on the same device: int32 [oh], int32
     [oh], fp32 [oh, taps_y] and the same per output column (tokensgen_amd.video_io.resample_plan builds them)."""
     _chk(frames_u8, "frames", torch.uint8)
-    if frames_u8.dim() != 4 or frames_u8.shape[-1] != 3 or not frames_u8.is_contiguous():
-        raise ValueError(f"frames: expected contiguous [F, H, W, 3], got {tuple(frames_u8.shape)}")
+    (_, F, H, W), _ = _chk_rgb(frames_u8, "frames", contiguous=True)
     y0, ny, wy, x0, nx, wx = tables
     for t, name, dt, n in ((y0, "y0", torch.int32, oh), (ny, "ny", torch.int32, oh), (wy, "wy", torch.float32, oh), (x0, "x0", torch.int32, ow),
                            (nx, "nx", torch.int32, ow), (wx, "wx", torch.float32, ow)):
         _chk(t, name, dt)
         if t.device != frames_u8.device or not t.is_contiguous() or t.shape[0] != n or t.dim() != (2 if dt == torch.float32 else 1):
             raise ValueError(f"{name}: expected a contiguous table of {n} rows on {frames_u8.device}, got {tuple(t.shape)} on {t.device}")
-    F, H, W, _ = frames_u8.shape
     out = torch.empty(F, 3, oh, ow, dtype=BF16, device=frames_u8.device)
     L.check(_launch("video_resample", L.load().tg_video_resample, _p(frames_u8), F, H, W, _p(out), oh, ow, _p(y0), _p(ny), _p(wy), wy.shape[1], _p(x0), _p(nx),
                     _p(wx), wx.shape[1], _stream()), "tg_video_resample")
@@ -933,40 +955,51 @@ def _image_strides(t, layout):
     raise ValueError(f"layout {layout!r} does not describe a tensor of shape {tuple(t.shape)} (hwc: [F, H, W, C] / [B, T, H, W, C]; chw: [n, C, H, W]; bcthw; bfchw)")
 
 
+def _image_args(tensors, layout, crop_border, channels, min_side, least):
+    """What the wrappers that read an image batch share, everything but the device: tensors ((t, name), ..) of one dtype (uint8, fp32, bf16) and one shape in `layout`
+    (IMAGE_LAYOUTS), any views; C must be one of `channels`, and the plane without `crop_border` pixels on every side at least min_side x min_side (`least` names that
+    in the refusal).  -> (n_outer, n_inner, C, H, W, h, w, the tensors' element strides, their base offsets in elements: where the cropped plane starts)"""
+    for t, name in tensors:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: expected a tensor")
+        if t.dtype not in _IMAGE_DTYPES:
+            raise TypeError(f"{name}: expected uint8, float32 or bfloat16, got {t.dtype}")
+    first, rest = tensors[0][0], [t for t, _ in tensors[1:]]
+    if any(t.dtype != first.dtype for t in rest):
+        raise TypeError(f"a and b must have one dtype, got {first.dtype} and {rest[0].dtype}")
+    if layout not in IMAGE_LAYOUTS:
+        raise ValueError(f"layout must be one of {sorted(IMAGE_LAYOUTS)}, got {layout!r}")
+    if any(t.shape != first.shape for t in rest):
+        raise ValueError(f"image shapes are different: {tuple(first.shape)}, {tuple(rest[0].shape)}")
+    (n_outer, n_inner, Cn, H, W), _ = _image_strides(first, layout)
+    strides = [_image_strides(t, layout)[1] for t, _ in tensors]
+    if Cn not in channels:
+        raise ValueError(f"expected {' or '.join(map(str, channels))} channels, got {Cn}")
+    cb = int(crop_border)
+    h, w = H - 2 * cb, W - 2 * cb
+    if cb < 0 or h < min_side or w < min_side:
+        raise ValueError(f"a {H} x {W} plane with crop_border {cb} is smaller than {least}")
+    if n_outer * n_inner < 1:
+        raise ValueError("no images")
+    if min(min(st) for st in strides) < 0:
+        raise ValueError("views with negative strides are not supported")
+    return n_outer, n_inner, Cn, H, W, h, w, strides, [cb * (st[3] + st[4]) for st in strides]
+
+
 def image_metrics(a, b, layout, crop_border=0, y_only=False):
     """tg_image_metrics: per image plane of two equally shaped uint8 (0..255), fp32 or bf16 (in [0, 1]) image batches, float64 [n_outer, n_inner, planes, 2] =
     (sum of squared differences on the 0..255 scale over the plane, sum of the SSIM map over its (h - 10) x (w - 10) window positions), h x w the plane without
     `crop_border` pixels on every side; planes = C, or 1 with y_only (C == 3: BT.601 luma).  layout names the axes (IMAGE_LAYOUTS); a and b may be any views with
     non-negative strides, the crop costs no copy.  One call for all planes; a plane's numbers do not depend on the other planes of the call."""
-    for t, name in ((a, "a"), (b, "b")):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name}: expected a tensor")
-        if t.dtype not in _IMAGE_DTYPES:
-            raise TypeError(f"{name}: expected uint8, float32 or bfloat16, got {t.dtype}")
-    if a.dtype != b.dtype:
-        raise TypeError(f"a and b must have one dtype, got {a.dtype} and {b.dtype}")
-    if layout not in IMAGE_LAYOUTS:
-        raise ValueError(f"layout must be one of {sorted(IMAGE_LAYOUTS)}, got {layout!r}")
-    if a.shape != b.shape:
-        raise ValueError(f"image shapes are different: {tuple(a.shape)}, {tuple(b.shape)}")
-    (n_outer, n_inner, Cn, H, W), sa = _image_strides(a, layout)
-    _, sb = _image_strides(b, layout)
-    if Cn not in (1, 3) or (y_only and Cn != 3):
-        raise ValueError(f"expected 1 or 3 channels (3 with y_only), got {Cn}")
-    cb = int(crop_border)
-    h, w = H - 2 * cb, W - 2 * cb
-    if cb < 0 or h < IMAGE_WINDOW or w < IMAGE_WINDOW:
-        raise ValueError(f"a {H} x {W} plane with crop_border {cb} is smaller than the {IMAGE_WINDOW} x {IMAGE_WINDOW} window")
-    if n_outer * n_inner < 1:
-        raise ValueError("no images")
+    n_outer, n_inner, Cn, _, _, h, w, (sa, sb), (oa, ob) = _image_args(((a, "a"), (b, "b")), layout, crop_border, (3,) if y_only else (1, 3), IMAGE_WINDOW,
+                                                                       f"the {IMAGE_WINDOW} x {IMAGE_WINDOW} window")
     if not (a.is_cuda and b.is_cuda) or a.device != b.device:
         raise RuntimeError("image_metrics: expected two tensors on one GPU (tokensgen_amd has no CPU fallback)")
     lib = L.load()
     planes = n_outer * n_inner * (1 if y_only else Cn)
     ws = torch.empty(lib.tg_image_metrics_ws_doubles(planes, h, w), dtype=torch.float64, device=a.device)
     out = torch.empty(n_outer, n_inner, planes // (n_outer * n_inner), 2, dtype=torch.float64, device=a.device)
-    pa = a.data_ptr() + cb * (sa[3] + sa[4]) * a.element_size()
-    pb = b.data_ptr() + cb * (sb[3] + sb[4]) * b.element_size()
+    pa, pb = a.data_ptr() + oa * a.element_size(), b.data_ptr() + ob * b.element_size()
     L.check(_launch("image_metrics", lib.tg_image_metrics, pa, *sa, pb, *sb, _IMAGE_DTYPES[a.dtype], n_outer, n_inner, Cn, h, w, int(bool(y_only)), _p(ws), _p(out),
                     _stream()), "tg_image_metrics")
     return out
@@ -980,20 +1013,9 @@ def lpips_conv_in(x, layout, weight, bias, out, crop_border=0, normalize=False, 
     plane without `crop_border` pixels on every side).  x: uint8 (0..255), fp32 or bf16 (in [-1, 1], or in [0, 1] with normalize) in one of IMAGE_LAYOUTS with 3
     channels, any view with non-negative strides.  outer: only that outer index; inner = (first, count): only those inner indices (a chunk of a clip: a base offset,
     no copy); F = the images taken.  weight fp32 [64, 27], bias fp32 [64]."""
-    if not isinstance(x, torch.Tensor) or x.dtype not in _IMAGE_DTYPES:
-        raise TypeError(f"x: expected a uint8, float32 or bfloat16 tensor, got {getattr(x, 'dtype', type(x))}")
-    if layout not in IMAGE_LAYOUTS:
-        raise ValueError(f"layout must be one of {sorted(IMAGE_LAYOUTS)}, got {layout!r}")
-    (n_outer, n_inner, Cn, H, W), st = _image_strides(x, layout)
-    if Cn != 3:
-        raise ValueError(f"expected 3 channels, got {Cn}")
-    cb = int(crop_border)
-    h, w = H - 2 * cb, W - 2 * cb
-    if cb < 0 or h < LPIPS_MIN_SIDE or w < LPIPS_MIN_SIDE:
-        raise ValueError(f"a {H} x {W} image with crop_border {cb} is smaller than {LPIPS_MIN_SIDE} x {LPIPS_MIN_SIDE}")
+    n_outer, n_inner, _, _, _, h, w, (st,), (off,) = _image_args(((x, "x"),), layout, crop_border, (3,), LPIPS_MIN_SIDE, f"{LPIPS_MIN_SIDE} x {LPIPS_MIN_SIDE}")
     if normalize and x.dtype == torch.uint8:
         raise ValueError("normalize is for float inputs in [0, 1]; uint8 frames are read as 2 (v / 255) - 1")
-    off = cb * (st[3] + st[4])
     if outer is not None:
         if not 0 <= outer < n_outer:
             raise ValueError(f"outer index {outer} out of range 0..{n_outer - 1}")
@@ -1003,8 +1025,6 @@ def lpips_conv_in(x, layout, weight, bias, out, crop_border=0, normalize=False, 
         if not (0 <= first and count >= 1 and first + count <= n_inner):
             raise ValueError(f"inner range {inner} out of range 0..{n_inner}")
         off, n_inner = off + first * st[1], count
-    if n_outer * n_inner < 1:
-        raise ValueError("no images")
     if tuple(weight.shape) != (64, 27) or tuple(bias.shape) != (64,) or not weight.is_contiguous() or not bias.is_contiguous():
         raise ValueError(f"weight / bias: expected contiguous [64, 27] / [64], got {tuple(weight.shape)} / {tuple(bias.shape)}")
     if tuple(out.shape) != (n_outer * n_inner, h, w, 64) or not out.is_contiguous():
@@ -1203,74 +1223,16 @@ def text_alignment(img, txt):
 MOTION_BLOCKS, MOTION_MAX_RADIUS = (8, 16), 32
 
 
-def _rgb_strides(t):
-    """(n_outer, n_inner, H, W) and the byte strides (outer, inner, row, pixel, channel) of uint8 [F, H, W, 3] / [B, T, H, W, 3] frames (any view)"""
-    s = t.stride()
-    if t.dim() == 4:
-        return (1, t.shape[0], t.shape[1], t.shape[2]), (0, s[0], s[1], s[2], s[3])
-    return (t.shape[0], t.shape[1], t.shape[2], t.shape[3]), (s[0], s[1], s[2], s[3], s[4])
-
-
-def _chk_frames(t, name):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"{name}: expected a GPU tensor (tokensgen_amd has no CPU fallback)")
-    if t.dtype != torch.uint8 or t.dim() not in (4, 5) or t.shape[-1] != 3 or min(t.stride()) < 0:
-        raise ValueError(f"{name}: expected uint8 [F, H, W, 3] or [B, T, H, W, 3] with non-negative strides, got {t.dtype} {tuple(t.shape)}")
-    return t
-
-
 def luma_u8(frames):
     """tg_luma_u8: uint8 RGB frames [F, H, W, 3] / [B, T, H, W, 3] (any view) -> uint8 luma planes [n_outer, n_inner, H, pitch], pitch = W rounded up to a multiple of
     4 (pad bytes 0); Y = (77 R + 150 G + 29 B + 128) >> 8."""
-    _chk_frames(frames, "frames")
-    (no, ni, H, W), st = _rgb_strides(frames)
+    (no, ni, H, W), st = _chk_rgb(frames, "frames")
     if no * ni < 1 or H < 1 or W < 1:
         raise ValueError(f"luma_u8: no pixels in {tuple(frames.shape)}")
     lib = L.load()
     out = torch.empty(no, ni, H, lib.tg_luma_pitch(W), dtype=torch.uint8, device=frames.device)
     L.check(_launch("luma_u8", lib.tg_luma_u8, _p(frames), *st, no, ni, H, W, _p(out), _stream()), "tg_luma_u8")
     return out
-
-
-def block_motion(cur, ref, width, block, radius):
-    """tg_block_motion: cur, ref uint8 luma planes [n_outer, n_inner, H, pitch] from luma_u8 (views along the first two axes allowed: a video's planes 0 .. T - 2 and
-    1 .. T - 1), width = the planes' true W.  Returns mv int16 [n_outer, n_inner, Hb, Wb, 2] (dy, dx), sad and sad0 int32 [n_outer, n_inner, Hb, Wb]."""
-    for t, name in ((cur, "cur"), (ref, "ref")):
-        _chk(t, name, torch.uint8)
-    if cur.dim() != 4 or cur.shape != ref.shape or cur.stride()[2:] != (cur.shape[3], 1) or ref.stride()[2:] != (ref.shape[3], 1):
-        raise ValueError(f"block_motion: expected two equally shaped stacks of packed planes [n_outer, n_inner, H, pitch], got {tuple(cur.shape)} and {tuple(ref.shape)}")
-    no, ni, H, pitch = cur.shape
-    block, radius, W = int(block), int(radius), int(width)
-    if block not in MOTION_BLOCKS or not 1 <= radius <= MOTION_MAX_RADIUS or no * ni < 1 or not block <= W <= pitch or H < block:
-        raise ValueError(f"block_motion: block {block} (8 or 16), radius {radius} (1..{MOTION_MAX_RADIUS}), planes {tuple(cur.shape)} of width {W}")
-    Hb, Wb = H // block, W // block
-    mv = torch.empty(no, ni, Hb, Wb, 2, dtype=torch.int16, device=cur.device)
-    sad = torch.empty(2, no, ni, Hb, Wb, dtype=torch.int32, device=cur.device)
-    L.check(_launch("block_motion", L.load().tg_block_motion, _p(cur), cur.stride(0), cur.stride(1), _p(ref), ref.stride(0), ref.stride(1), no, ni, H, W, pitch, block,
-                    radius, _p(mv), _p(sad[0]), _p(sad[1]), _stream()), "tg_block_motion")
-    return mv, sad[0], sad[1]
-
-
-def block_warp_sse(cur, ref, mv, block):
-    """tg_block_warp_sse: cur, ref uint8 RGB frames of one shape ([F, H, W, 3] / [B, T, H, W, 3], any views), pair i of cur against pair i of ref; mv int16
-    [n_outer, n_inner, Hb, Wb, 2] contiguous.  Returns sse, sse0 int32 [n_outer, n_inner, Hb, Wb] and status int32 [1] (vectors that had to be clamped)."""
-    _chk_frames(cur, "cur"); _chk_frames(ref, "ref"); _chk(mv, "mv", torch.int16)
-    (no, ni, H, W), sa = _rgb_strides(cur)
-    _, sb = _rgb_strides(ref)
-    block = int(block)
-    if cur.shape != ref.shape or block not in MOTION_BLOCKS or no * ni < 1 or H < block or W < block:
-        raise ValueError(f"block_warp_sse: frames {tuple(cur.shape)} and {tuple(ref.shape)} with block {block}")
-    Hb, Wb = H // block, W // block
-    if tuple(mv.shape) != (no, ni, Hb, Wb, 2) or not mv.is_contiguous():
-        raise ValueError(f"block_warp_sse: mv must be contiguous [{no}, {ni}, {Hb}, {Wb}, 2], got {tuple(mv.shape)}")
-    sse = torch.empty(2, no, ni, Hb, Wb, dtype=torch.int32, device=cur.device)
-    status = torch.zeros(1, dtype=torch.int32, device=cur.device)
-    L.check(_launch("block_warp_sse", L.load().tg_block_warp_sse, _p(cur), *sa, _p(ref), *sb, _p(mv), no, ni, H, W, block, _p(sse[0]), _p(sse[1]), _p(status),
-                    _stream()), "tg_block_warp_sse")
-    return sse[0], sse[1], status
-
-
-MCI_FACTORS = (2, 8)
 
 
 def _chk_planes(prev, nxt, width, block, who):
@@ -1282,6 +1244,41 @@ def _chk_planes(prev, nxt, width, block, who):
     if block not in MOTION_BLOCKS or no * ni < 1 or not block <= int(width) <= pitch or H < block:
         raise ValueError(f"{who}: block {block} (8 or 16), planes {tuple(prev.shape)} of width {width}")
     return no, ni, H, pitch
+
+
+def block_motion(cur, ref, width, block, radius):
+    """tg_block_motion: cur, ref uint8 luma planes [n_outer, n_inner, H, pitch] from luma_u8 (views along the first two axes allowed: a video's planes 0 .. T - 2 and
+    1 .. T - 1), width = the planes' true W.  Returns mv int16 [n_outer, n_inner, Hb, Wb, 2] (dy, dx), sad and sad0 int32 [n_outer, n_inner, Hb, Wb]."""
+    block, radius, W = int(block), int(radius), int(width)
+    no, ni, H, pitch = _chk_planes(cur, ref, W, block, "block_motion")
+    if not 1 <= radius <= MOTION_MAX_RADIUS:
+        raise ValueError(f"block_motion: radius must be in 1..{MOTION_MAX_RADIUS}, got {radius}")
+    Hb, Wb = H // block, W // block
+    mv = torch.empty(no, ni, Hb, Wb, 2, dtype=torch.int16, device=cur.device)
+    sad = torch.empty(2, no, ni, Hb, Wb, dtype=torch.int32, device=cur.device)
+    L.check(_launch("block_motion", L.load().tg_block_motion, _p(cur), cur.stride(0), cur.stride(1), _p(ref), ref.stride(0), ref.stride(1), no, ni, H, W, pitch, block,
+                    radius, _p(mv), _p(sad[0]), _p(sad[1]), _stream()), "tg_block_motion")
+    return mv, sad[0], sad[1]
+
+
+def block_warp_sse(cur, ref, mv, block):
+    """tg_block_warp_sse: cur, ref uint8 RGB frames of one shape ([F, H, W, 3] / [B, T, H, W, 3], any views), pair i of cur against pair i of ref; mv int16
+    [n_outer, n_inner, Hb, Wb, 2] contiguous.  Returns sse, sse0 int32 [n_outer, n_inner, Hb, Wb] and status int32 [1] (vectors that had to be clamped)."""
+    (no, ni, H, W), sa = _chk_rgb(cur, "cur")
+    _, sb = _chk_rgb(ref, "ref")
+    block = int(block)
+    if cur.shape != ref.shape or block not in MOTION_BLOCKS or no * ni < 1 or H < block or W < block:
+        raise ValueError(f"block_warp_sse: frames {tuple(cur.shape)} and {tuple(ref.shape)} with block {block}")
+    Hb, Wb = H // block, W // block
+    _chk_vec(mv, "mv", torch.int16, (no, ni, Hb, Wb, 2))
+    sse = torch.empty(2, no, ni, Hb, Wb, dtype=torch.int32, device=cur.device)
+    status = torch.zeros(1, dtype=torch.int32, device=cur.device)
+    L.check(_launch("block_warp_sse", L.load().tg_block_warp_sse, _p(cur), *sa, _p(ref), *sb, _p(mv), no, ni, H, W, block, _p(sse[0]), _p(sse[1]), _p(status),
+                    _stream()), "tg_block_warp_sse")
+    return sse[0], sse[1], status
+
+
+MCI_FACTORS = (2, 8)
 
 
 def mci_select(prev, nxt, fwd, bwd, width, block, factor):
@@ -1296,9 +1293,7 @@ def mci_select(prev, nxt, fwd, bwd, width, block, factor):
     for t, name in ((fwd, "fwd"), (bwd, "bwd")):
         if t is None and name == "bwd":
             continue
-        _chk(t, name, torch.int16)
-        if tuple(t.shape) != (no, ni, Hb, Wb, 2) or not t.is_contiguous():
-            raise ValueError(f"mci_select: {name} must be contiguous [{no}, {ni}, {Hb}, {Wb}, 2], got {tuple(t.shape)}")
+        _chk_vec(t, name, torch.int16, (no, ni, Hb, Wb, 2))
     mvi = torch.empty(no, ni, n - 1, Hb, Wb, 2, dtype=torch.int16, device=prev.device)
     cost = torch.empty(no, ni, n - 1, Hb, Wb, dtype=torch.int32, device=prev.device)
     L.check(_launch("mci_select", L.load().tg_mci_select, _p(prev), prev.stride(0), prev.stride(1), _p(nxt), nxt.stride(0), nxt.stride(1), _p(fwd),
@@ -1309,19 +1304,16 @@ def mci_select(prev, nxt, fwd, bwd, width, block, factor):
 def mci_render(prev, nxt, mvi, block, factor, out):
     """tg_mci_render: prev, nxt uint8 RGB frames of one shape ([B, P, H, W, 3], any views), mvi int16 [B, P, factor - 1, Hb, Wb, 2] contiguous; out uint8
     [B, P * factor + 1, H, W, 3] contiguous: frame i * factor + k of out is written for every pair i and phase k = 1 .. factor - 1, the frames i * factor are left alone."""
-    _chk_frames(prev, "prev"); _chk_frames(nxt, "next"); _chk(mvi, "mvi", torch.int16); _chk_frames(out, "out")
+    (no, ni, H, W), sa = _chk_rgb(prev, "prev")
+    _, sb = _chk_rgb(nxt, "next")
     block, n = int(block), int(factor)
     if prev.dim() != 5 or prev.shape != nxt.shape or block not in MOTION_BLOCKS or not MCI_FACTORS[0] <= n <= MCI_FACTORS[1]:
         raise ValueError(f"mci_render: frames {tuple(prev.shape)} and {tuple(nxt.shape)} ([B, P, H, W, 3]) with block {block}, factor {n}")
-    (no, ni, H, W), sa = _rgb_strides(prev)
-    _, sb = _rgb_strides(nxt)
     if no * ni < 1 or H < block or W < block:
         raise ValueError(f"mci_render: frames {tuple(prev.shape)} hold no {block} x {block} block")
     Hb, Wb = H // block, W // block
-    if tuple(mvi.shape) != (no, ni, n - 1, Hb, Wb, 2) or not mvi.is_contiguous():
-        raise ValueError(f"mci_render: mvi must be contiguous [{no}, {ni}, {n - 1}, {Hb}, {Wb}, 2], got {tuple(mvi.shape)}")
-    if tuple(out.shape) != (no, ni * n + 1, H, W, 3) or not out.is_contiguous():
-        raise ValueError(f"mci_render: out must be contiguous [{no}, {ni * n + 1}, {H}, {W}, 3], got {tuple(out.shape)}")
+    _chk_vec(mvi, "mvi", torch.int16, (no, ni, n - 1, Hb, Wb, 2))
+    _chk_vec(out, "out", torch.uint8, (no, ni * n + 1, H, W, 3))
     L.check(_launch("mci_render", L.load().tg_mci_render, _p(prev), *sa, _p(nxt), *sb, _p(mvi), no, ni, H, W, block, n, _p(out), out.stride(0), out.stride(1),
                     _stream()), "tg_mci_render")
     return out
@@ -1331,20 +1323,9 @@ COLOR_MODES = {"meanstd": 0, "histogram": 1}
 COLOR_MAX_WINDOW = 64
 
 
-def _chk_u8_frames(t, name):
-    """contiguous uint8 [F, H, W, 3] on the GPU -> (F, H, W)"""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"{name}: expected a GPU tensor (tokensgen_amd has no CPU fallback)")
-    if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[-1] != 3 or not t.is_contiguous() or t.numel() < 1:
-        raise ValueError(f"{name}: expected contiguous uint8 [F, H, W, 3] with at least one pixel, got {t.dtype} {tuple(t.shape)}")
-    if t.shape[1] * t.shape[2] >= 1 << 31:
-        raise ValueError(f"{name}: a frame of {t.shape[1]} x {t.shape[2]} pixels reaches 2^31")
-    return t.shape[0], t.shape[1], t.shape[2]
-
-
 def color_hist_u8(frames):
     """tg_color_hist_u8: contiguous uint8 [F, H, W, 3] -> int32 [F, 3, 256], the counts per frame, channel and value (exact; a frame's counts depend on it alone)."""
-    F, H, W = _chk_u8_frames(frames, "color_hist_u8")
+    (_, F, H, W), _ = _chk_rgb(frames, "color_hist_u8", contiguous=True)
     out = torch.empty(F, 3, 256, dtype=torch.int32, device=frames.device)
     L.check(_launch("color_hist_u8", L.load().tg_color_hist_u8, _p(frames), F, H, W, _p(out), _stream()), "tg_color_hist_u8")
     return out
@@ -1353,11 +1334,10 @@ def color_hist_u8(frames):
 def color_match_lut(hist, anchor, mode, strength, window, max_gain, history=None, status=None):
     """tg_color_match_lut: hist int32 [F, 3, 256], anchor int64 [3, 256], history None or int32 [n, 3, 256] (the n < window frames before the call's, oldest first)
     -> (lut uint8 [F, 3, 256], status int32 [1]: the number of (frame, channel) histograms the device refused and gave the identity table)."""
-    _chk(hist, "hist", torch.int32); _chk(anchor, "anchor", torch.int64)
+    _chk(hist, "hist", torch.int32)
     if hist.dim() != 3 or tuple(hist.shape[1:]) != (3, 256) or hist.shape[0] < 1 or not hist.is_contiguous():
         raise ValueError(f"color_match_lut: hist must be contiguous [F, 3, 256], got {tuple(hist.shape)}")
-    if tuple(anchor.shape) != (3, 256) or not anchor.is_contiguous():
-        raise ValueError(f"color_match_lut: anchor must be contiguous [3, 256], got {tuple(anchor.shape)}")
+    _chk_vec(anchor, "anchor", torch.int64, (3, 256))
     n_hist = 0
     if history is not None and history.shape[0] > 0:
         _chk(history, "history", torch.int32)
@@ -1377,13 +1357,11 @@ def color_match_lut(hist, anchor, mode, strength, window, max_gain, history=None
 def color_apply_lut(frames, lut, out=None):
     """tg_color_apply_lut: out[f, y, x, c] = lut[f, c, frames[f, y, x, c]]; frames contiguous uint8 [F, H, W, 3], lut uint8 [F, 3, 256] contiguous; out None (a new
     tensor), `frames` itself (in place) or another contiguous tensor of its shape."""
-    F, H, W = _chk_u8_frames(frames, "color_apply_lut")
-    _chk(lut, "lut", torch.uint8)
-    if tuple(lut.shape) != (F, 3, 256) or not lut.is_contiguous():
-        raise ValueError(f"color_apply_lut: lut must be contiguous [{F}, 3, 256], got {tuple(lut.shape)}")
+    (_, F, H, W), _ = _chk_rgb(frames, "color_apply_lut", contiguous=True)
+    _chk_vec(lut, "lut", torch.uint8, (F, 3, 256))
     if out is None:
         out = torch.empty_like(frames)
-    elif _chk_u8_frames(out, "color_apply_lut: out") != (F, H, W) or out.device != frames.device:
+    elif _chk_rgb(out, "color_apply_lut: out", contiguous=True)[0] != (1, F, H, W) or out.device != frames.device:
         raise ValueError(f"color_apply_lut: out must have the frames' shape {tuple(frames.shape)} and device, got {tuple(out.shape)}")
     L.check(_launch("color_apply_lut", L.load().tg_color_apply_lut, _p(frames), _p(lut), F, H, W, _p(out), _stream()), "tg_color_apply_lut")
     return out
@@ -1393,40 +1371,16 @@ def lab_metrics(a, b, layout, crop_border=0):
     """tg_lab_metrics: per frame of one (b None) or two equally shaped uint8 (0..255), fp32 or bf16 (in [0, 1]) RGB image batches the float64 sums over the h x w pixels
     (the plane without `crop_border` pixels on every side) of CIE L*, a*, b*, C*ab of `a` -> [n_outer, n_inner, 4], and with b also those of b and of the CIE76
     dE between them -> [n_outer, n_inner, 9].  layout, views and the crop as image_metrics; a frame's sums do not depend on the other frames of the call."""
-    for t, name in ((a, "a"), (b, "b")):
-        if t is None and name == "b":
-            continue
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name}: expected a tensor")
-        if t.dtype not in _IMAGE_DTYPES:
-            raise TypeError(f"{name}: expected uint8, float32 or bfloat16, got {t.dtype}")
-    if b is not None and a.dtype != b.dtype:
-        raise TypeError(f"a and b must have one dtype, got {a.dtype} and {b.dtype}")
-    if layout not in IMAGE_LAYOUTS:
-        raise ValueError(f"layout must be one of {sorted(IMAGE_LAYOUTS)}, got {layout!r}")
-    if b is not None and a.shape != b.shape:
-        raise ValueError(f"image shapes are different: {tuple(a.shape)}, {tuple(b.shape)}")
-    (n_outer, n_inner, Cn, H, W), sa = _image_strides(a, layout)
-    sb = _image_strides(b, layout)[1] if b is not None else (0, 0, 0, 0, 0)
-    if Cn != 3:
-        raise ValueError(f"expected 3 channels (RGB), got {Cn}")
-    cb = int(crop_border)
-    h, w = H - 2 * cb, W - 2 * cb
-    if cb < 0 or h < 1 or w < 1:
-        raise ValueError(f"a {H} x {W} plane with crop_border {cb} has no pixel left")
-    if n_outer * n_inner < 1:
-        raise ValueError("no images")
-    if min(sa + sb) < 0:
-        raise ValueError("views with negative strides are not supported")
+    n_outer, n_inner, _, _, _, h, w, st, off = _image_args(((a, "a"),) + (((b, "b"),) if b is not None else ()), layout, crop_border, (3,), 1, "one pixel")
     if not a.is_cuda or (b is not None and (not b.is_cuda or a.device != b.device)):
         raise RuntimeError("lab_metrics: expected tensors on one GPU (tokensgen_amd has no CPU fallback)")
     lib = L.load()
     ns = 4 if b is None else 9
     ws = torch.empty(lib.tg_lab_metrics_ws_doubles(n_outer * n_inner, h, w, int(b is not None)), dtype=torch.float64, device=a.device)
     out = torch.empty(n_outer, n_inner, ns, dtype=torch.float64, device=a.device)
-    pa = a.data_ptr() + cb * (sa[3] + sa[4]) * a.element_size()
-    pb = None if b is None else b.data_ptr() + cb * (sb[3] + sb[4]) * b.element_size()
-    L.check(_launch("lab_metrics", lib.tg_lab_metrics, pa, *sa, pb, *sb, _IMAGE_DTYPES[a.dtype], n_outer, n_inner, h, w, _p(ws), _p(out), _stream()), "tg_lab_metrics")
+    pa = a.data_ptr() + off[0] * a.element_size()
+    pb, sb = (None, (0, 0, 0, 0, 0)) if b is None else (b.data_ptr() + off[1] * b.element_size(), st[1])
+    L.check(_launch("lab_metrics", lib.tg_lab_metrics, pa, *st[0], pb, *sb, _IMAGE_DTYPES[a.dtype], n_outer, n_inner, h, w, _p(ws), _p(out), _stream()), "tg_lab_metrics")
     return out
 
 
@@ -1444,7 +1398,7 @@ def jpeg_geometry(H, W, subsampling, restart_interval=1):
 
 def jpeg_coeffs(frames, quality, subsampling):
     """tg_jpeg_coeffs: contiguous uint8 [F, H, W, 3] -> int16 [F, MCUs, blocks per MCU, 64], the quantised DCT coefficients in zigzag order (the header's definition)."""
-    F, H, W = _chk_u8_frames(frames, "jpeg_coeffs")
+    (_, F, H, W), _ = _chk_rgb(frames, "jpeg_coeffs", contiguous=True)
     rows, cols, bpm, _ = jpeg_geometry(H, W, subsampling)
     coef = torch.empty(F, rows * cols, bpm, 64, dtype=torch.int16, device=frames.device)
     L.check(_launch("jpeg_coeffs", L.load().tg_jpeg_coeffs, _p(frames), F, H, W, JPEG_SUBSAMPLINGS[subsampling], int(quality), _p(coef), _stream()), "tg_jpeg_coeffs")
@@ -1471,10 +1425,9 @@ def jpeg_segment_bytes(coef, H, W, subsampling, restart_interval):
 def jpeg_write(coef, H, W, quality, subsampling, restart_interval, seg_offsets, frame_offsets, data):
     """tg_jpeg_write: the header and the segments of every frame into `data` (uint8 [n]) at frame_offsets (int64 [F]) and seg_offsets (int64 [F, n_seg])."""
     F, n_seg = _chk_jpeg_coef(coef, H, W, subsampling, restart_interval, "jpeg_write")
-    _chk(seg_offsets, "seg_offsets", torch.int64); _chk(frame_offsets, "frame_offsets", torch.int64); _chk(data, "data", torch.uint8)
-    if tuple(seg_offsets.shape) != (F, n_seg) or not seg_offsets.is_contiguous() or tuple(frame_offsets.shape) != (F,) or data.dim() != 1:
-        raise ValueError(f"jpeg_write: seg_offsets contiguous [{F}, {n_seg}], frame_offsets [{F}], data [n]; got {tuple(seg_offsets.shape)}, {tuple(frame_offsets.shape)}, "
-                         f"{tuple(data.shape)}")
+    _chk_vec(seg_offsets, "seg_offsets", torch.int64, (F, n_seg)); _chk_vec(frame_offsets, "frame_offsets", torch.int64, (F,)); _chk(data, "data", torch.uint8)
+    if data.dim() != 1:
+        raise ValueError(f"jpeg_write: data must be uint8 [n], got {tuple(data.shape)}")
     L.check(_launch("jpeg_write", L.load().tg_jpeg_write, _p(coef), F, H, W, JPEG_SUBSAMPLINGS[subsampling], int(quality), int(restart_interval), _p(seg_offsets),
                     _p(frame_offsets), _p(data), data.numel(), _stream()), "tg_jpeg_write")
     return data
@@ -1504,12 +1457,6 @@ def jpeg_decode_segments(H, W, subsampling, restart_interval):
     if not n:
         raise ValueError(f"jpeg: a frame of {H} x {W} (1..65535), subsampling {subsampling!r} ({sorted(JPEG_SUBSAMPLINGS)}), restart_interval {restart_interval!r} (0..65535)")
     return n
-
-
-def _chk_vec(t, name, dtype, shape):
-    _chk(t, name, dtype)
-    if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-        raise ValueError(f"{name}: expected contiguous {list(shape)}, got {tuple(t.shape)}")
 
 
 def jpeg_find_segments(data, scan_begin, scan_end, n_seg, status):
@@ -1615,7 +1562,7 @@ def png_geometry(H, W, rows_per_block=0):
 def png_filter(frames, filter, rows_per_block=0):
     """tg_png_filter: contiguous uint8 [F, H, W, 3] -> uint8 [F, workspace bytes of a frame]: every row's filter type and filtered bytes, a band's rows together and
     every band at a multiple of 16 bytes (the header's definition)."""
-    F, H, W = _chk_u8_frames(frames, "png_filter")
+    (_, F, H, W), _ = _chk_rgb(frames, "png_filter", contiguous=True)
     if filter not in PNG_FILTERS:
         raise ValueError(f"png_filter: filter must be one of {tuple(PNG_FILTERS)}, got {filter!r}")
     ws = png_geometry(H, W, rows_per_block)[3]
@@ -1644,10 +1591,9 @@ def png_band_plan(filtered, H, W, rows_per_block=0):
 def png_write(filtered, plans, H, W, rows_per_block, band_offsets, data):
     """tg_png_write: every frame's file into `data` (uint8 [n]); band_offsets int64 [F, bands]: where every band's IDAT chunk starts."""
     F, g = _chk_png_filtered(filtered, H, W, rows_per_block, "png_write")
-    _chk(plans, "plans", torch.uint8); _chk(band_offsets, "band_offsets", torch.int64); _chk(data, "data", torch.uint8)
-    if tuple(plans.shape) != (F, g[1], g[4]) or not plans.is_contiguous() or tuple(band_offsets.shape) != (F, g[1]) or not band_offsets.is_contiguous() or data.dim() != 1:
-        raise ValueError(f"png_write: plans contiguous [{F}, {g[1]}, {g[4]}], band_offsets contiguous [{F}, {g[1]}], data [n]; got {tuple(plans.shape)}, "
-                         f"{tuple(band_offsets.shape)}, {tuple(data.shape)}")
+    _chk_vec(plans, "plans", torch.uint8, (F, g[1], g[4])); _chk_vec(band_offsets, "band_offsets", torch.int64, (F, g[1])); _chk(data, "data", torch.uint8)
+    if data.dim() != 1:
+        raise ValueError(f"png_write: data must be uint8 [n], got {tuple(data.shape)}")
     L.check(_launch("png_write", L.load().tg_png_write, _p(filtered), _p(plans), F, H, W, int(rows_per_block), _p(band_offsets), _p(data), data.numel(), _stream()),
             "tg_png_write")
     return data

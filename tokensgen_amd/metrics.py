@@ -303,7 +303,7 @@ def video_motion(frames, block=16, radius=16, top_fraction=0.05):
     frames.  Returns float64 device tensors: the per-pair curves of motion.summarize — "magnitude", "magnitude_top", "static_fraction", "flicker", "residual" — shaped
     [F - 1] / [B, T - 1], and "<curve>_mean", their 0-dim means over all pairs.  A near-still video has magnitude 0 and static_fraction 1 whatever its consistency
     scores say; a jump at a clip join shows as a spike of `residual`.  Nothing here waits for the device."""
-    M.check_frames(frames, "video_motion")
+    M.check_pairs(frames, "video_motion")
     M.check_block(block, radius, frames.shape[-3], frames.shape[-2], "video_motion")
     M.top_count(top_fraction, 1)
     out, _ = _motion_curves(frames, block, radius, top_fraction)
@@ -331,7 +331,7 @@ def video_warp_error(frames, motion_from=None, block=16, radius=16):
     "warp_psnr" = 10 log10(1 / (mse + 1e-8)) (video_metrics' formula), "still_mse" / "still_psnr" the same at zero displacement; pooled 0-dim "warp_mse_mean",
     "warp_psnr_pooled" = the PSNR of the mean mse, "still_mse_mean", "still_psnr_pooled"; and "status" (int32 [1], always 0 here: searched vectors stay inside
     the frame).  Nothing here waits for the device."""
-    M.check_frames(frames, "video_warp_error", motion_from)
+    M.check_pairs(frames, "video_warp_error", motion_from)
     M.check_block(block, radius, frames.shape[-3], frames.shape[-2], "video_warp_error")
     mv = M.block_motion(frames if motion_from is None else motion_from, block, radius)["mv"]
     w = M.warp_sse(frames, mv)
@@ -349,7 +349,7 @@ def video_motion_smoothness(frames, block=16, radius=16):
     "blend_mse_mean", "blend_psnr_pooled" (the PSNR of the mean mse); and 0-dim "score" = 1 - mean |mc - truth| / 255 over all held-out bytes.  A video that moves
     smoothly is predictable from every other frame: mc_psnr high and well above blend_psnr.  The average and the absolute difference are torch arithmetic on the
     held-out frames; nothing here waits for the device."""
-    M.check_frames(frames, "video_motion_smoothness")
+    M.check_pairs(frames, "video_motion_smoothness")
     M.check_block(block, radius, frames.shape[-3], frames.shape[-2], "video_motion_smoothness")
     T = frames.shape[-4]
     if T < 3:
@@ -389,7 +389,7 @@ class VideoMotion:
     def update(self, frames, motion_from=None):
         if isinstance(frames, torch.Tensor) and frames.dim() != 4:
             raise ValueError(f"VideoMotion.update: one video's clip [F, H, W, 3], got {tuple(frames.shape)}")
-        M.check_frames(frames, "VideoMotion.update", motion_from, pairs_within=False)
+        M.check_pairs(frames, "VideoMotion.update", motion_from, pairs_within=False)
         M.check_block(self.block, self.radius, frames.shape[1], frames.shape[2], "VideoMotion.update")
         st = self._open
         if st is None:

@@ -16,18 +16,14 @@ import math
 import torch
 
 from . import kernels as K
+from .frames import check_frames, is_int
 
 BLOCKS, MAX_RADIUS, FACTORS = K.MOTION_BLOCKS, K.MOTION_MAX_RADIUS, K.MCI_FACTORS
 
 
-def check_frames(frames, who, ref=None, pairs_within=True):
-    """The shape contract of every entry point, checked before any kernel call.  Returns the number of pairs per batch item."""
-    if not isinstance(frames, torch.Tensor):
-        raise ValueError(f"{who}: expected a tensor of frames")
-    if frames.dtype != torch.uint8:
-        raise NotImplementedError(f"{who}: uint8 frames only (video_io's \"uint8\" output), got {frames.dtype}")
-    if frames.dim() not in (4, 5) or frames.shape[-1] != 3:
-        raise ValueError(f"{who}: expected [F, H, W, 3] or [B, T, H, W, 3], got {tuple(frames.shape)}")
+def check_pairs(frames, who, ref=None, pairs_within=True):
+    """frames.check_frames and what is motion's own, the second video and the pairs; checked before any kernel call.  Returns the number of pairs per batch item."""
+    check_frames(frames, who)
     if ref is not None:
         if not isinstance(ref, torch.Tensor):
             raise ValueError(f"{who}: expected a tensor as the second video")
@@ -45,7 +41,7 @@ def check_frames(frames, who, ref=None, pairs_within=True):
 def check_block(block, radius, H, W, who):
     if not isinstance(block, int) or block not in BLOCKS:
         raise ValueError(f"{who}: block must be one of {BLOCKS}, got {block!r}")
-    if radius is not None and (not isinstance(radius, int) or isinstance(radius, bool) or not 1 <= radius <= MAX_RADIUS):
+    if radius is not None and (not is_int(radius) or not 1 <= radius <= MAX_RADIUS):
         raise ValueError(f"{who}: radius must be an integer in 1..{MAX_RADIUS}, got {radius!r}")
     if H < block or W < block:
         raise ValueError(f"{who}: a {H} x {W} frame holds no {block} x {block} block")
@@ -55,7 +51,7 @@ def block_motion(frames, block=16, radius=16, ref=None):
     """Exhaustive block matching.  Returns {"mv": int16 [.., P, Hb, Wb, 2] as (dy, dx), "sad": int32 [.., P, Hb, Wb] the winner's cost, "sad0": int32 the cost at
     (0, 0)} on the device; P = F - 1 (T - 1 per batch item), or F (T) with `ref`.  The winner is the minimum of (sad, dy^2 + dx^2, dy, dx) over the candidates that
     keep the block inside the frame.  Nothing here waits for the device."""
-    P = check_frames(frames, "block_motion", ref, pairs_within=ref is None)
+    P = check_pairs(frames, "block_motion", ref, pairs_within=ref is None)
     H, W = frames.shape[-3], frames.shape[-2]
     check_block(block, radius, H, W, "block_motion")
     ya = K.luma_u8(frames)
@@ -74,7 +70,7 @@ def warp_sse(frames, mv, ref=None):
     """Motion-compensated squared error of uint8 RGB frames under given vectors (this video's or another's of the same shape): {"sse": int32 [.., P, Hb, Wb] =
     sum over the block and the channels of (cur - ref displaced by (dy, dx))^2, "sse0": the same at zero displacement, "status": int32 [1], the number of vectors
     that pointed out of the frame and were clamped (0 for vectors of block_motion)}.  The block size is read off mv's shape: H // Hb must be 8 or 16."""
-    P = check_frames(frames, "warp_sse", ref, pairs_within=ref is None)
+    P = check_pairs(frames, "warp_sse", ref, pairs_within=ref is None)
     H, W = frames.shape[-3], frames.shape[-2]
     if not isinstance(mv, torch.Tensor) or mv.dtype != torch.int16 or mv.dim() != frames.dim() or mv.shape[-1] != 2 or mv.shape[-2] < 1 or mv.shape[-3] < 1:
         raise ValueError(f"warp_sse: mv must be int16 [.., P, Hb, Wb, 2], got {getattr(mv, 'dtype', None)} {tuple(getattr(mv, 'shape', ()))}")
@@ -94,7 +90,7 @@ def warp_sse(frames, mv, ref=None):
 
 
 def check_factor(factor, who):
-    if not isinstance(factor, int) or isinstance(factor, bool) or not FACTORS[0] <= factor <= FACTORS[1]:
+    if not is_int(factor) or not FACTORS[0] <= factor <= FACTORS[1]:
         raise ValueError(f"{who}: factor must be an integer in {FACTORS[0]}..{FACTORS[1]}, got {factor!r}")
 
 
@@ -104,7 +100,7 @@ def interpolate_frames(frames, factor=2, block=16, radius=16, bidirectional=True
     depends on that pair's two frames alone.  The vectors of block_motion (prev -> next and, with `bidirectional`, next -> prev) give every block of an in-between
     frame its candidates; tg_mci_select picks one by the bilateral SAD, tg_mci_render blends the overlapping block predictions.  With return_vectors a dict
     {"video", "mvi": int16 [.., P, factor - 1, Hb, Wb, 2], "cost": int32 [.., P, factor - 1, Hb, Wb]}.  Nothing here waits for the device."""
-    P = check_frames(frames, "interpolate_frames")
+    P = check_pairs(frames, "interpolate_frames")
     H, W = frames.shape[-3], frames.shape[-2]
     check_factor(factor, "interpolate_frames")
     check_block(block, radius, H, W, "interpolate_frames")
@@ -137,7 +133,7 @@ class FrameRateUpsampler:
     def update(self, frames):
         if isinstance(frames, torch.Tensor) and frames.dim() != 4:
             raise ValueError(f"FrameRateUpsampler.update: one video's clip [F, H, W, 3], got {tuple(frames.shape)}")
-        check_frames(frames, "FrameRateUpsampler.update", pairs_within=False)
+        check_pairs(frames, "FrameRateUpsampler.update", pairs_within=False)
         check_block(self.block, self.radius, frames.shape[1], frames.shape[2], "FrameRateUpsampler.update")
         if self._last is not None and self._last.shape[1:] != frames.shape[1:]:
             raise ValueError(f"FrameRateUpsampler.update: the video's frames are {tuple(self._last.shape[1:])}, this clip's {tuple(frames.shape[1:])}")

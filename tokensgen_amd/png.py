@@ -7,7 +7,7 @@ reference code: the header's comment is the definition, tests/png_ref.py restate
 jpeg.encode_jpeg.  Row filters, run-length tokens and one Huffman block per band of rows, all in integers: a frame is one exact byte string, the same alone and in a
 batch, and any PNG reader returns the frame's bytes exactly.  The sizing pass and the writing pass are separated by the one host read of an encode, the total size.
 
-uint8 RGB frames only ("uint8" of video_io.VideoProcessor).  Every refusal comes before any kernel call.  There is no CPU path.  Not here: APNG, reading PNG, 16-bit,
+uint8 RGB frames only ("uint8" of video_io.VideoProcessor; the contract: frames.py).  Every refusal comes before any kernel call.  There is no CPU path.  Not here: APNG, reading PNG, 16-bit,
 palette, alpha and grey images, LZ77 matches beyond distance 1."""
 import os
 from typing import NamedTuple
@@ -15,7 +15,7 @@ from typing import NamedTuple
 import torch
 
 from . import kernels as K
-from .jpeg import check_device, _is_int
+from .frames import check_device, check_frames, is_int, single_frame, split_bytes
 
 FILTERS = tuple(K.PNG_FILTERS)
 MAX_BAND_BYTES = 65535
@@ -37,29 +37,18 @@ class PngGeometry(NamedTuple):
 
 def png_geometry(H, W, rows_per_block=None):
     """How an H x W frame is cut into bands; pure Python, no device.  rows_per_block None: min(DEFAULT_ROWS_PER_BLOCK, what fits MAX_BAND_BYTES)."""
-    if not _is_int(H) or not _is_int(W) or not 1 <= H <= MAX_HEIGHT or W < 1:
+    if not is_int(H) or not is_int(W) or not 1 <= H <= MAX_HEIGHT or W < 1:
         raise ValueError(f"png: a frame is 1..{MAX_HEIGHT} rows of at least one pixel, got {H!r} x {W!r}")
     if W > MAX_WIDTH:
         raise ValueError(f"png: a row of {W} pixels is {1 + 3 * W} filtered bytes; a band is at most {MAX_BAND_BYTES} bytes, so W <= {MAX_WIDTH}")
     row = 1 + 3 * W
     if rows_per_block is None:
         rows_per_block = min(DEFAULT_ROWS_PER_BLOCK, MAX_BAND_BYTES // row)
-    if not _is_int(rows_per_block) or rows_per_block < 1 or rows_per_block * row > MAX_BAND_BYTES:
+    if not is_int(rows_per_block) or rows_per_block < 1 or rows_per_block * row > MAX_BAND_BYTES:
         raise ValueError(f"png: rows_per_block must be an integer in 1..{MAX_BAND_BYTES // row} for W = {W} (a band is at most {MAX_BAND_BYTES} bytes), "
                          f"got {rows_per_block!r}")
     bands = -(-H // rows_per_block)
     return PngGeometry(rows_per_block, bands, row, rows_per_block * row, FILE_HEADER_BYTES + FILE_TRAILER_BYTES + 8 + bands * 17 + H * row)
-
-
-def check_frames(frames, who, dims=(4, 5)):
-    """The shape contract of every entry point, checked before any kernel call; the wording of jpeg.check_frames."""
-    if not isinstance(frames, torch.Tensor):
-        raise ValueError(f"{who}: expected a tensor of frames")
-    if frames.dtype != torch.uint8:
-        raise NotImplementedError(f"{who}: uint8 frames only (video_io's \"uint8\" output), got {frames.dtype}")
-    want = " or ".join({3: "[H, W, 3]", 4: "[F, H, W, 3]", 5: "[B, T, H, W, 3]"}[d] for d in dims)
-    if frames.dim() not in dims or frames.shape[-1] != 3 or frames.numel() < 1:
-        raise ValueError(f"{who}: expected {want} (RGB, three channels) with at least one pixel, got {tuple(frames.shape)}")
 
 
 def check_params(filter, who):
@@ -98,20 +87,17 @@ def encode_png(frames, filter="adaptive", rows_per_block=None):
 
 def png_bytes(frames, filter="adaptive", rows_per_block=None):
     """encode_png, copied to the host and cut: a list of one `bytes` per frame."""
-    data, offsets = encode_png(frames, filter, rows_per_block)
-    host, o = data.cpu().numpy().tobytes(), offsets.tolist()
-    return [host[o[i]:o[i + 1]] for i in range(len(o) - 1)]
+    return split_bytes(*encode_png(frames, filter, rows_per_block))
 
 
 def save_png(frame, path, filter="adaptive", rows_per_block=None):
     """One frame, uint8 [H, W, 3] (or [1, H, W, 3]) on the device, as a .png file; returns the path."""
     check_frames(frame, "save_png", dims=(3, 4))
-    if frame.dim() == 4 and frame.shape[0] != 1:
-        raise ValueError(f"save_png: one frame per file, got {frame.shape[0]}")
+    one = single_frame(frame, "save_png")
     check_params(filter, "save_png")
     png_geometry(frame.shape[-3], frame.shape[-2], rows_per_block)
     check_device(frame, "save_png")
-    (b,) = png_bytes(frame.reshape(1, *frame.shape[-3:]), filter, rows_per_block)
+    (b,) = png_bytes(one, filter, rows_per_block)
     with open(path, "wb") as fh:
         fh.write(b)
     return path
@@ -119,7 +105,7 @@ def save_png(frame, path, filter="adaptive", rows_per_block=None):
 
 def sequence_paths(pattern, n, start=0):
     """pattern.format(start), ..., pattern.format(start + n - 1); refused where the pattern does not give n different names"""
-    if not isinstance(pattern, (str, os.PathLike)) or not _is_int(start) or start < 0:
+    if not isinstance(pattern, (str, os.PathLike)) or not is_int(start) or start < 0:
         raise ValueError(f"save_png_sequence: pattern must be a path with one number field such as 'frame_{{:05d}}.png' and start an integer >= 0, got {pattern!r}, {start!r}")
     try:
         paths = [os.fspath(pattern).format(start + i) for i in range(n)]

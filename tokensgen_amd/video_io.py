@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import kernels as K
+from .frames import gpu_device
 
 MAX_TAPS = 64          # tg_video_resample refuses more (about 15x downscaling)
 
@@ -146,17 +147,6 @@ def _device_tables(plan, device):
     return plan._device[key]
 
 
-def _gpu(device):
-    dev = torch.device(device) if device is not None else None
-    if dev is None:
-        if not torch.cuda.is_available():
-            raise RuntimeError("tokensgen_amd.video_io needs a GPU (tokensgen_amd has no CPU fallback)")
-        dev = torch.device("cuda", torch.cuda.current_device())
-    if dev.type != "cuda":
-        raise RuntimeError(f"tokensgen_amd.video_io needs a GPU device, got {dev} (tokensgen_amd has no CPU fallback)")
-    return torch.device("cuda", torch.cuda.current_device()) if dev.index is None and torch.cuda.is_available() else dev
-
-
 def prepare_video(frames_u8, output_res=(480, 720), crop_to_fit=False, pad_to_fit=False, device=None):
     """Decoded frames, uint8 [F, H, W, 3] (torch tensor or numpy array), -> bf16 [1, F, 3, oh, ow] in [-1, 1] on the GPU: what `load_video` returns
     (long_video.py:61-76) and `vae_encode_image` / `pipe(frames=...)` take.  See resample_plan for the two branches.  The result does not depend on how many frames one
@@ -165,7 +155,7 @@ def prepare_video(frames_u8, output_res=(480, 720), crop_to_fit=False, pad_to_fi
         frames_u8 = torch.from_numpy(frames_u8)
     if not isinstance(frames_u8, torch.Tensor) or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
         raise TypeError("prepare_video: expected uint8 frames [F, H, W, 3]")
-    dev = _gpu(device if device is not None else (frames_u8.device if frames_u8.is_cuda else None))
+    dev = gpu_device(device if device is not None else (frames_u8.device if frames_u8.is_cuda else None), "tokensgen_amd.video_io")
     plan = resample_plan(frames_u8.shape[1:3], output_res, crop_to_fit, pad_to_fit)
     out = K.video_resample(frames_u8.to(dev).contiguous(), _device_tables(plan, dev), *plan.output_res)
     return out[None]
