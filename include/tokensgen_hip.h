@@ -1084,6 +1084,49 @@ int tg_png_band_plan(const void* filtered, int F, int H, int W, int rows_per_blo
 int tg_png_write(const void* filtered, const void* plans, int F, int H, int W, int rows_per_block, const void* band_offsets, void* data, long data_bytes,
                  hipStream_t stream);
 
+/* Reading PNG (csrc/png_decode.hip, csrc/png_inflate.h): the zlib streams of a batch of frames -> uint8 [F, H, W, 3], exact.  tests/png_dec_ref.py
+ * restates this comment.  The host (tokensgen_amd.png.parse_png) reads the container: it joins a frame's IDAT payloads into the frame's zlib stream, checks the two
+ * header bytes and takes the four Adler bytes off the end; what the kernels see are byte ranges of raw deflate data (RFC 1951) inside one buffer.
+ *   A piece is data[begin, end), its frame, and whether it is the frame's last.  All frames of a call are H x W with bpp 3 (colour type 2) or 4 (colour type 6), 8
+ *   bits; a frame's filtered bytes are H rows of 1 + bpp W: n = H (1 + bpp W) bytes.
+ *   Mode 0, "stream": one piece per frame, the whole deflate stream.  Blocks are decoded up to the one with BFINAL; fewer than 8 bits may be left behind it, and the
+ *   output must be exactly n bytes.
+ *   Modes 1 and 2, "chunk": a piece is one IDAT payload of a stream that is cut into independent pieces.  A piece must be whole blocks ending exactly at its end (no bit
+ *   left) with no BFINAL, except the last piece, which must end with the BFINAL block (fewer than 8 bits behind it) and whose output must end at n; no distance may
+ *   reach before the piece's own first output byte.  Mode 1 stores only piece_bytes[p], the bytes the piece decodes to; the caller forms piece_at as the exclusive
+ *   prefix sum inside each frame; mode 2 writes piece p's bytes at filtered[frame][piece_at[p] ...].  A piece that breaks a rule sets bit 256 beside the rule's own
+ *   bit; the caller then decodes the call by mode 0, whose answer counts.
+ *   status int32 [F], zeroed by the caller, bits ORed in; a piece stops at its first error, and nothing is ever signalled by a fault:
+ *       1  block type 3, or a stored block whose LEN is not ~NLEN
+ *       2  bad code lengths, by the rules of zlib's inflate_table: an over-subscribed code; an incomplete code-length or literal/length code; an incomplete distance
+ *          code other than a single code of length 1 (no distance code at all is allowed); no end-of-block code; HLIT above 286 or HDIST above 30 symbols; a repeat
+ *          (16) with nothing before it; a repeat running past HLIT + HDIST.  The two sets of lengths are one sequence: a repeat may cross from one into the other.
+ *       4  an invalid symbol: a bit pattern that is no code, a length symbol 286 or 287, a distance symbol 30 or 31
+ *       8  a distance that reaches before the first byte of the frame's output (mode 0)
+ *      16  the input ends inside a block (also: fewer than 15 bits are left and they begin no code)
+ *      32  the output is not exactly n bytes (a token that would pass n stops the piece), or 8 or more bits are left behind the final block
+ *      64  the Adler-32 of the filtered bytes is not the stream's (tg_png_unfilter, from the pieces' pairs)
+ *     128  a filter type above 4 (tg_png_unfilter; the row is read as type 0)
+ *     256  chunk modes only: the piece is not independent; a verdict, not an error
+ *     512  a byte range or an index outside its buffer
+ *   Order: of a block the header is checked first (1, 2), then its tokens in order; of a token the symbol (4, 16), the distance (8 / 256), the size (32).
+ *   Unfiltering.  Arithmetic modulo 256; x the filtered byte, a the byte bpp to the left, b the byte above, c the byte above a, zeros outside the image: none x, sub
+ *   x + a, up x + b, average x + floor((a + b) / 2) on the 9-bit sum, paeth x + the one of a, b, c nearest to a + b - c, in that order on ties.  The fourth byte of a
+ *   pixel (bpp 4) takes no part in the other three and is dropped.
+ * tg_png_decode_geometry(H, W, bpp, what): 0 bytes of a filtered row, 1 of a frame's filtered bytes, 2 lanes per piece, 3 bytes of the output ring; 0 for refused
+ *   arguments (H, W >= 1, bpp 3 or 4, H (1 + bpp W) and 3 H W below 2^31).  Pure host function.
+ * tg_png_inflate: piece_begin, piece_end, piece_at int64 [pieces]; piece_frame, piece_last, piece_bytes int32 [pieces]; adler3 uint32 [pieces, 3] (modes 0 and 2: A, B
+ *   and the byte count of the piece, as Adler-32 pairs combine); filtered uint8 [F, n].  A range outside [0, data_bytes) or a frame index outside [0, F) sets 512 and
+ *   decodes nothing.  One wave per piece; every read is inside the piece's range, every store inside its frame's n bytes.
+ * tg_png_unfilter: frame_first int32 [F + 1]: the pieces of frame f are frame_first[f] .. frame_first[f + 1]; expect uint32 [F]: the streams' Adler-32.  A frame whose
+ *   status is not 0 after the comparison is zeros.
+ * Neither allocates, copies or waits. */
+long tg_png_decode_geometry(int H, int W, int bpp, int what);
+int tg_png_inflate(const void* data, long data_bytes, const void* piece_begin, const void* piece_end, const void* piece_frame, const void* piece_last, int pieces,
+                   int mode, const void* piece_at, void* filtered, int F, int H, int W, int bpp, void* piece_bytes, void* adler3, void* status, hipStream_t stream);
+int tg_png_unfilter(const void* filtered, int F, int H, int W, int bpp, const void* frame_first, const void* adler3, const void* expect, void* status, void* rgb,
+                    hipStream_t stream);
+
 /* Dispatch overrides for the cross-check tests — NOT part of the operator surface.  The library reads no environment variable and keeps no other
  * process-wide state: the defaults are the shipped path, and these knobs only choose between two PRODUCT kernels of the same operator (each pair is held
  * bitwise or to rounding against each other by tests/).  Knobs: TG_ATTN_PP_MIN_WG (1024: workgroups from which the 8-wave attention kernel is used),

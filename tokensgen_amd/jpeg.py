@@ -509,7 +509,7 @@ def load_video(video_path, output_res, nf_per_chunk, pad_to_fit, sample_fps, sta
     from . import video_io
     ext = os.path.splitext(str(video_path))[1].lower()
     if ext != ".avi":
-        raise ValueError(f"load_video: {video_path!r}: only the Motion-JPEG .avi format is read (no {ext or 'suffix-less'} decoder here)")
+        raise ValueError(f"load_video: {video_path!r}: only the Motion-JPEG .avi format and numbered .png sequences are read (no {ext or 'suffix-less'} decoder here)")
     with MJPEGReader(video_path, device) as r:
         idx = video_io.sample_frame_indices(len(r), r.get_avg_fps(), nf_per_chunk, sample_fps, start_t, end_t, max_num_chunks)
         frames = r.get_batch(idx.tolist())

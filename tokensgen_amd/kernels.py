@@ -1597,3 +1597,55 @@ def png_write(filtered, plans, H, W, rows_per_block, band_offsets, data):
     L.check(_launch("png_write", L.load().tg_png_write, _p(filtered), _p(plans), F, H, W, int(rows_per_block), _p(band_offsets), _p(data), data.numel(), _stream()),
             "tg_png_write")
     return data
+
+
+# the bits of the PNG decoder's status (the list of include/tokensgen_hip.h) and what each says
+PNG_STATUS = {1: "a block of type 3, or a stored block whose LEN is not ~NLEN", 2: "code lengths that are no prefix code", 4: "an invalid symbol",
+              8: "a distance that reaches before the start of the output", 16: "the zlib stream ends inside a block",
+              32: "the stream does not decode to exactly the frame's bytes, or does not end where the last IDAT ends", 64: "the Adler-32 does not match",
+              128: "a filter type above 4", 256: "a piece of the stream is not independent", 512: "a byte range or index outside its buffer"}
+PNG_INFLATE_MODES = {"stream": 0, "chunk_size": 1, "chunk_write": 2}
+
+
+def png_decode_geometry(H, W, bpp):
+    """tg_png_decode_geometry: (bytes of a filtered row, of a frame's filtered bytes, lanes per piece, bytes of the output ring); refused arguments raise."""
+    lib = L.load()
+    g = tuple(lib.tg_png_decode_geometry(H, W, bpp, what) for what in range(4))
+    if not all(g):
+        raise ValueError(f"png: a frame of {H} x {W} pixels of {bpp} bytes (3 or 4) whose filtered bytes, H (1 + bpp W), and 3 H W stay below 2^31")
+    return g
+
+
+def png_inflate(data, pieces, mode, filtered, H, W, bpp, status, piece_at=None):
+    """tg_png_inflate: data uint8 [n]; pieces = (begin int64 [P], end int64 [P], frame int32 [P], last int32 [P]); filtered uint8 [F, frame bytes]; status int32 [F].
+    mode "chunk_size" returns piece_bytes int32 [P]; "stream" and "chunk_write" (with piece_at int64 [P]) return adler3 uint32-as-int32 [P, 3]."""
+    begin, end, frame, last = pieces
+    P, F = begin.numel(), status.numel()
+    _chk(data, "data", torch.uint8); _chk_vec(begin, "piece_begin", torch.int64, (P,)); _chk_vec(end, "piece_end", torch.int64, (P,))
+    _chk_vec(frame, "piece_frame", torch.int32, (P,)); _chk_vec(last, "piece_last", torch.int32, (P,)); _chk_vec(status, "status", torch.int32, (F,))
+    _chk_vec(filtered, "filtered", torch.uint8, (F, png_decode_geometry(H, W, bpp)[1]))
+    if mode not in PNG_INFLATE_MODES or data.dim() != 1 or not data.is_contiguous():
+        raise ValueError(f"png_inflate: mode is one of {tuple(PNG_INFLATE_MODES)} and data contiguous uint8 [n], got {mode!r}, {tuple(data.shape)}")
+    sizes = adler3 = None
+    if mode == "chunk_size":
+        sizes = torch.empty(P, dtype=torch.int32, device=data.device)
+    else:
+        adler3 = torch.empty(P, 3, dtype=torch.int32, device=data.device)
+    if mode == "chunk_write":
+        _chk_vec(piece_at, "piece_at", torch.int64, (P,))
+    L.check(_launch("png_inflate", L.load().tg_png_inflate, _p(data), data.numel(), _p(begin), _p(end), _p(frame), _p(last), P, PNG_INFLATE_MODES[mode],
+                    _p(piece_at) if mode == "chunk_write" else None, _p(filtered), F, H, W, bpp, _p(sizes) if sizes is not None else None,
+                    _p(adler3) if adler3 is not None else None, _p(status), _stream()), "tg_png_inflate")
+    return sizes if mode == "chunk_size" else adler3
+
+
+def png_unfilter(filtered, H, W, bpp, frame_first, adler3, expect, status):
+    """tg_png_unfilter: filtered uint8 [F, frame bytes] -> uint8 [F, H, W, 3]; frame_first int32 [F + 1], adler3 int32 [P, 3], expect int32 [F] (the bits of the
+    streams' Adler-32), status int32 [F]."""
+    F = status.numel()
+    _chk_vec(filtered, "filtered", torch.uint8, (F, png_decode_geometry(H, W, bpp)[1])); _chk_vec(frame_first, "frame_first", torch.int32, (F + 1,))
+    _chk_vec(expect, "expect", torch.int32, (F,)); _chk_vec(status, "status", torch.int32, (F,)); _chk(adler3, "adler3", torch.int32)
+    out = torch.empty(F, H, W, 3, dtype=torch.uint8, device=filtered.device)
+    L.check(_launch("png_unfilter", L.load().tg_png_unfilter, _p(filtered), F, H, W, bpp, _p(frame_first), _p(adler3), _p(expect), _p(status), _p(out), _stream()),
+            "tg_png_unfilter")
+    return out

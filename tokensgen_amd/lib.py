@@ -114,6 +114,8 @@ PROTOTYPES = {
     "tg_png_filter": [_vp, _i, _i, _i, _i, _i, _vp, _vp],
     "tg_png_band_plan": [_vp, _i, _i, _i, _i, _vp, _vp, _vp],
     "tg_png_write": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _l, _vp],
+    "tg_png_inflate": [_vp, _l, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "tg_png_unfilter": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "tg_conv3d_cl": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _l, _i, _i, _i, _vp, _vp, _vp, _vp],
     "tg_conv3d_up2_subpixel": [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _l, _i, _vp, _vp, _vp],
     "tg_groupnorm_finalize": [_vp, _l, _i, _f, _vp, _vp],
@@ -167,6 +169,7 @@ QUERIES = {
     "tg_jpeg_idct_ws_bytes": [C.c_int] * 4,
     "tg_jpeg_sync_ws_bytes": [C.c_int] * 5,
     "tg_png_geometry": [C.c_int] * 4,
+    "tg_png_decode_geometry": [C.c_int] * 4,
 }
 
 TG_BWD_ONE_KERNEL = 1

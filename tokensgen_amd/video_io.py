@@ -4,7 +4,8 @@ Front end: the arithmetic of `load_video` (longvgen/data/long_video.py:28-76) af
 then `video / 255.` -> resize -> crop / pad -> `* 2 - 1` (:61-76) with `resize_for_rectangle_crop` (longvgen/data/utils.py:112-140, bicubic, centre crop) or
 `ResolutionControl.__call__` (utils.py:13-107, optional pad with -1, bilinear to exactly output_res), in one launch of tg_video_resample (csrc/video.hip).
 `prepare_video` takes the uint8 [F, H, W, 3] frames a decoder delivers; `load_video` is the whole function for Motion-JPEG .avi files, decoded on the device by
-tokensgen_amd.jpeg; there is no decoder library here, so every other container is refused by name.
+tokensgen_amd.jpeg, and for numbered PNG sequences (tokensgen_amd.png, §8o); there is no decoder library here, so every other container is refused by
+name.
 
 STATED ASSUMPTION: torchvision 0.19.1 `resize` defaults to antialias=True and, on a float tensor, is
 `F.interpolate(img, size, mode, align_corners=False, antialias=True)` without a clamp; torchvision's source is absent, so that call is taken as the definition and
@@ -16,6 +17,7 @@ from the "np" output, formed on the device (a quarter of the float32 transfer). 
 
 Not registered under the `longvgen.data` alias (tokensgen_amd.compat): the dataset classes are out of scope."""
 import functools
+import os
 from types import SimpleNamespace
 
 import numpy as np
@@ -243,10 +245,24 @@ def load_video(video_path, output_res, nf_per_chunk, pad_to_fit, sample_fps, sta
     """The first step of the reference's entry script (`load_video`, long_video.py:28-76, same parameter order): a Motion-JPEG .avi file (one that `export_to_video`
     wrote, or any baseline MJPG AVI) -> bf16 [1, F, 3, oh, ow] in [-1, 1] on the device.  The file's index is read on the host, `sample_frame_indices` picks the
     frames, they are decoded on the device (tokensgen_amd.jpeg.MJPEGReader; a file without restart markers in parallel inside each frame, §8m) and go
-    through `prepare_video`.  Any other suffix is refused: there is no
-    H.264 / mp4 decoder here.  The JPEG code is imported by the first call."""
+    through `prepare_video`.  A path with the suffix .png is the pattern of a numbered sequence of PNG frames ("clip/frame_{:05d}.png", what `save_png_sequence` writes
+    and any tool can produce from an .mp4), read at 8 frames a second, the rate `export_to_video` writes by default: `load_image_sequence`, DESIGN.md §8o.  Any other
+    suffix is refused: there is no H.264 / mp4 decoder here.  The JPEG or PNG code is imported by the first call."""
+    if os.path.splitext(str(video_path))[1].lower() == ".png":
+        return load_image_sequence(video_path, output_res, nf_per_chunk, pad_to_fit, sample_fps, start_t, end_t, max_num_chunks, crop_to_fit, device)
     from . import jpeg
     return jpeg.load_video(video_path, output_res, nf_per_chunk, pad_to_fit, sample_fps, start_t, end_t, max_num_chunks, crop_to_fit, device)
+
+
+def load_image_sequence(video_path, output_res, nf_per_chunk, pad_to_fit, sample_fps, start_t, end_t, max_num_chunks, crop_to_fit=False, device=None, fps=8, start=0):
+    """`load_video` for a numbered sequence of PNG frames: video_path is the pattern ("clip/frame_{:05d}.png"), `start` the first number; the files that exist in a row
+    from there are the clip.  A sequence has no rate of its own: `fps` says what the frames are, and `sample_frame_indices` works with it as with a container's.  The
+    frames asked for are decoded on the device (tokensgen_amd.png.PNGSequenceReader) and go through `prepare_video`."""
+    from . import png
+    with png.PNGSequenceReader(video_path, fps, start, device) as r:
+        idx = sample_frame_indices(len(r), r.get_avg_fps(), nf_per_chunk, sample_fps, start_t, end_t, max_num_chunks)
+        frames = r.get_batch(idx.tolist())
+    return prepare_video(frames, output_res, crop_to_fit, pad_to_fit, device)
 
 
 def export_to_video(video_frames, output_video_path, fps=8, quality=90):
